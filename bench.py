@@ -9,6 +9,11 @@ frozen X W1^T GEMM and both SpMMs are recomputed every iteration exactly as upst
 
 Prints ONE JSON line (see README / DESIGN.md for the field contract).  Launch for N > 1:
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times ONE region of exactly --steps steps and prints the headline (value, ms_per_step, config).
+--full adds everything else the line has carried: the roofline and per-kernel timings, the stage tables, the informational
+extras rates, the CPU baseline with post-delete parity, the N > 1 replicas rate and planner estimate, and five regions when
+--steps < 100.  --dump-outputs DIR writes what the timed steps computed (the Del weights and the last step's losses) as .npy.
 """
 import argparse
 import json
@@ -62,13 +67,18 @@ def parse():
     p.add_argument('--unroll', type=int, default=4, help='training iterations captured per hipGraph launch')
     p.add_argument('--no_cached_rate', action='store_true')
     p.add_argument('--repeats', type=int, default=0,
-                   help='timed regions of exactly --steps steps each; the MEDIAN region is reported (0 = 5 when --steps < 100, '
-                        'else 1): a 20-step region is 14 ms, shorter than the clock / power ramp of the part')
+                   help='timed regions of exactly --steps steps each; the MEDIAN region is reported (0 = one region; with --full, '
+                        '5 when --steps < 100, else 1: a 20-step region is 14 ms, shorter than the clock / power ramp of the part)')
     p.add_argument('--stage_profile', default=None,
                    help='per-stage in-step kernel durations + PMC traffic from the committed rocprofv3 runs (tools/rocpd_stage_table.py); '
                         'default profiles/r06_final_stages.json (gcn) / profiles/r06_final_stages_<gnn>.json / ..._<workload>_<gnn>.json')
     p.add_argument('--probe_partition', action='store_true', help=argparse.SUPPRESS)   # child-process self test
     p.add_argument('--probe_overlap', action='store_true', help=argparse.SUPPRESS)     # ... of the overlapped exchanges
+    p.add_argument('--full', action='store_true',
+                   help='also measure everything beyond the headline (roofline, per-kernel and stage figures, extras rates, CPU '
+                        'baseline and parity, N > 1 replicas rate and planner estimate); off by default')
+    p.add_argument('--dump-outputs', dest='dump_outputs', default=None, metavar='DIR',
+                   help="after the timed steps, write their results (W_D1, W_D2, the last step's losses) to DIR/<name>.npy")
     p.add_argument('--parallel', default='auto', choices=['auto', 'partition', 'replicas'],
                    help='N>1: "auto" and "partition" = ONE request row-partitioned over the GPUs (RCCL halo all-to-all + '
                         'all-reduce per step) is the headline at every N, "scaling": "strong" - what north_star asks to be '
@@ -81,6 +91,28 @@ def parse():
         tag = ('' if a.gnn == 'gcn' else f'_{a.gnn}') if a.workload == 'synth-collab' else f"_{a.workload.replace('synth-', '').replace('-', '_')}_{a.gnn}"
         a.stage_profile = os.path.join(ROOT, 'profiles', f'r06_final_stages{tag}.json')
     return a
+
+
+def timed_regions(args):
+    """How many regions of exactly --steps steps are timed (the median is reported): --repeats, else one - or, under --full,
+    five when --steps < 100."""
+    if args.repeats > 0:
+        return args.repeats
+    return 5 if args.full and args.steps < 100 else 1
+
+
+def dump_outputs(out_dir, model, eng):
+    """What a caller of the timed Del steps receives, after the last one: both Del weights (float32) and that step's logged
+    losses (train_loss, loss_r, loss_l; float64) as out_dir/<name>.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    hist = eng.loss_history()
+    arrays = {'W_D1': model.deletion1.deletion_weight.detach().float().cpu().numpy(),
+              'W_D2': model.deletion2.deletion_weight.detach().float().cpu().numpy(),
+              'loss_last_step': hist[(eng.steps_done - 1) % hist.shape[0]].double().numpy() if len(hist) else np.full(3, np.nan)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
 
 
 def build_request(args, device):
@@ -345,11 +377,13 @@ def kg_main(args, device, rank=0, world=1, group=None, barrier=lambda: None, ctl
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX, group=ctl)
             dt_ = float(tmax)
         return dt_
-    n_regions = args.repeats if args.repeats > 0 else (5 if args.steps < 100 else 1)
+    n_regions = timed_regions(args)
     region_s = [timed_region() for _ in range(n_regions)]
     dt = sorted(region_s)[len(region_s) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, eng)
     units = args.steps if (partitioned or world == 1) else world * args.steps
-    per_rank = gather_halo_bytes(eng, world, ctl) if partitioned else None
+    per_rank = gather_halo_bytes(eng, world, ctl) if (partitioned and args.full) else None
     if rank != 0:
         return
     if world > 1:
@@ -359,10 +393,11 @@ def kg_main(args, device, rank=0, world=1, group=None, barrier=lambda: None, ctl
                'config': {'workload': f'{args.workload} R-GCN 2-layer, {args.df_size}% {args.df.upper()} triple deletion, full-graph fused Del step',
                           'num_nodes': data.num_nodes, 'hip_graph': not args.no_graph,
                           'parallelism': f'row-partition x{world} (typed halo all-to-all + all-reduce)' if partitioned else f'replicas x{world}',
-                          'ranks_seen': world, 'halo': eng.halo_report() if partitioned else None,
-                          'halo_recv_send_bytes_per_rank': per_rank},
+                          'ranks_seen': world, 'halo': eng.halo_report() if partitioned else None},
                'timing': {'regions': n_regions, 'ms_per_step_each_region': [1e3 * t / args.steps for t in region_s]},
                'final_loss': float(eng.loss_history()[-1, 0])}
+        if args.full and partitioned:
+            out['config']['halo_recv_send_bytes_per_rank'] = per_rank
         print(json.dumps(out))
         return
     out = {'metric': 'Del-op train iters/sec', 'value': args.steps / dt, 'unit': 'iters/s', 'n_gpus': 1, 'steps': args.steps,
@@ -374,7 +409,11 @@ def kg_main(args, device, rank=0, world=1, group=None, barrier=lambda: None, ctl
                       'num_nodes': data.num_nodes, 'typed_edges_dr': int(data.dr_mask.sum()), 'df_triples': int(data.directed_df_edge_index.shape[1]),
                       'S1': int(ni1.sum()), 'S2': int(ni2.sum()), 'hip_graph': not args.no_graph,
                       'matrix_products': matrix_products_label(), 'parallelism': 'single'},
-           'roofline': time_typed_conv(eng), 'final_loss': float(eng.loss_history()[-1, 0])}
+           'final_loss': float(eng.loss_history()[-1, 0])}
+    if not args.full:
+        print(json.dumps(out))
+        return
+    out['roofline'] = time_typed_conv(eng)
     if not args.no_cached_rate:
         # informational only (never `value`): the epoch as delete_gnn.py --fullgraph runs it by default - the frozen conv1 output
         # computed once, conv2's input gradient only on the Del-1 rows that read it (identical Del weights, tests/test_engine_gpu.py)
@@ -505,12 +544,14 @@ def nodecls_main(args, device, rank=0, world=1, barrier=lambda: None, ctl=None):
                 dt_ = float(tmax)
             out_.append(dt_)
         return out_
-    n_regions = args.repeats if args.repeats > 0 else (5 if args.steps < 100 else 1)
+    n_regions = timed_regions(args)
     eng = engine()
     region_s = rate(eng, n_regions)
     dt = sorted(region_s)[len(region_s) // 2]
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, eng)
     out = {'metric': 'Del-op train iters/sec', 'value': world * args.steps / dt, 'unit': 'iters/s', 'n_gpus': world, 'steps': args.steps,
            'warmup': args.warmup, 'ms_per_step': 1e3 * dt / args.steps, 'higher_is_better': True, 'scaling': 'weak',
            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
@@ -526,7 +567,7 @@ def nodecls_main(args, device, rank=0, world=1, barrier=lambda: None, ctl=None):
            'timing': {'regions': n_regions, 'steps_per_region': args.steps, 'reported': 'median region',
                       'ms_per_step_each_region': [1e3 * t / args.steps for t in region_s]},
            'final_loss': float(eng.loss_history()[-1, 0])}
-    if world > 1:
+    if world > 1 or not args.full:
         print(json.dumps(out))
         return
     prof, prof_note = load_stage_profile(args.stage_profile, data.num_nodes, eng.graph.nnz)
@@ -755,7 +796,7 @@ def median_rate(eng, args, regions=None):
     """iters/s of an engine the way the headline is timed: warm-up, then `regions` regions of exactly
     --steps steps each (5 when --steps < 100: a 20-step region is shorter than the clock ramp of the part), the MEDIAN
     region.  -> (rate, [ms per step of every region])."""
-    regions = regions or (args.repeats if args.repeats > 0 else (5 if args.steps < 100 else 1))
+    regions = regions or timed_regions(args)
     if args.unroll > 1 and not args.no_graph and hasattr(eng, 'prepare_unrolled'):
         eng.prepare_unrolled(args.unroll)
     for _ in range(args.warmup):
@@ -1260,13 +1301,14 @@ def main():
         return
     auto_est = None
     if auto and world > 1 and mode == 'partition':
-        # measure the single-GPU step on every rank (= the replicas rate reported under extras) and print the planner's estimate
-        # next to the measured partitioned step.  The HEADLINE stays the partitioned step at every N (a curve whose
-        # points switch between strong and weak scaling cannot be read); `--parallel replicas` asks for the other headline.
-        rep_rate_auto = replicas_rate(args, model, state, device, world, barrier)
-        share, share_src = layer1_share(args.stage_profile)
-        auto_est = partition_estimate(eng, world, ctl, 1e6 * world / rep_rate_auto, l1_share=share, l1_source=share_src)
-        auto_est['chosen'] = 'partition'
+        # --full: measure the single-GPU step on every rank (= the replicas rate reported under extras) and print the planner's
+        # estimate next to the measured partitioned step.  The HEADLINE stays the partitioned step at every N (a curve
+        # whose points switch between strong and weak scaling cannot be read); `--parallel replicas` asks for the other headline.
+        if args.full:
+            rep_rate_auto = replicas_rate(args, model, state, device, world, barrier)
+            share, share_src = layer1_share(args.stage_profile)
+            auto_est = partition_estimate(eng, world, ctl, 1e6 * world / rep_rate_auto, l1_share=share, l1_source=share_src)
+            auto_est['chosen'] = 'partition'
         model.load_state_dict(state)
         eng = make_engine(args, data, model, neg, ni1, ni2, device, rank, world, group)    # fresh state for the timed run
     if mode != 'partition':
@@ -1297,24 +1339,19 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX, group=ctl)
             dt_ = float(tmax)
         return dt_
-    n_regions = args.repeats if args.repeats > 0 else (5 if args.steps < 100 else 1)
+    n_regions = timed_regions(args)
     region_s = [timed_region() for _ in range(n_regions)]
     dt = sorted(region_s)[len(region_s) // 2]
     losses = eng.loss_history()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, eng)
 
     partitioned = mode == 'partition'
     units = args.steps if partitioned else world * args.steps      # iterations of whole requests
-    per_rank_halo = gather_halo_bytes(eng, world, ctl) if (partitioned and world > 1) else None
+    per_rank_halo = gather_halo_bytes(eng, world, ctl) if (args.full and partitioned and world > 1) else None
     rep_rate = (rep_rate_auto if auto_est is not None else replicas_rate(args, model, state, device, world, barrier)) \
-        if (partitioned and world > 1) else None
+        if (args.full and partitioned and world > 1) else None
     if rank == 0:
-        kdur_b2b, kbytes = time_dominant_kernel(eng)
-        kdur_ctx = time_dominant_kernel_in_context(eng) if world == 1 else None
-        kdur = kdur_ctx if kdur_ctx else kdur_b2b           # (in the step's context where that can be measured: see the function)
-        achieved = kbytes / kdur / 1e9
-        prof, prof_note = load_stage_profile(args.stage_profile, data.num_nodes, eng.graph.nnz) if world == 1 else ({}, 'N > 1')
-        traffic = prof.get('stages', {}).get('spmm1', {}).get('traffic_bytes')
-        ceil_ = fabric_ceiling(data.num_nodes, eng.graph.nnz, 128)
         out = {
             'metric': 'Del-op train iters/sec', 'value': units / dt, 'unit': 'iters/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': 1e3 * dt / args.steps,
@@ -1333,49 +1370,61 @@ def main():
                        'matrix_products': matrix_products_label(),
                        'parallelism': 'single' if world == 1 else (f'row-partition x{world} (RCCL halo all-to-all + all-reduce)'
                                                                   if partitioned else f'replicas x{world}')},
-            'roofline': {'kernel': 'spmm_persist_kernel<32,1,4,true,true> (layer-1 CSR SpMM, d=128)', 'bound': 'hbm',
-                         'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
-                         'traffic': traffic,
-                         # the recorded L2-miss (fabric) bytes over this run's launch duration: how close the kernel
-                         # runs to the ~6.3 TB/s a streaming copy achieves on this part (MI355X_MICROARCH.md)
-                         'traffic_gbs': traffic / kdur / 1e9 if traffic else None,
-                         'traffic_unit': ('bytes/launch (PMC FETCH_SIZE x2 + WRITE_SIZE, separate --pmc passes of this command: '
-                                          + os.path.relpath(args.stage_profile, ROOT) + ')') if prof else None,
-                         'stage_profile': os.path.relpath(args.stage_profile, ROOT) if prof else prof_note,
-                         'algorithmic_bytes': kbytes, 'avg_us': kdur * 1e6,
-                         'timing': ('HIP events around 20 (x W1^T; SpMM) pairs minus 20 x W1^T alone: the launch behind the kernel that '
-                                    'precedes it in the step' if kdur_ctx else 'HIP events around 20 back-to-back launches'),
-                         'back_to_back_us': kdur_b2b * 1e6, 'frac_back_to_back': kbytes / kdur_b2b / 1e9 / HBM_PEAK_GBS,
-                         'in_step_us': prof.get('stages', {}).get('spmm1', {}).get('in_step_us'),
-                         # what any kernel with one contiguous row range per XCD can reach on this graph (measurement):
-                         # the private L2s make the fabric carry every x row once per XCD that gathers it
-                         'ceiling_frac_on_this_graph': ceil_['frac'] if ceil_ else None, 'ceiling': ceil_},
             'final_loss': float(losses[-1, 0]) if len(losses) else None,
             'timing': {'regions': n_regions, 'steps_per_region': args.steps, 'reported': 'median region',
                        'ms_per_step_each_region': [1e3 * t / args.steps for t in region_s]},
         }
-        if args.gnn == 'gat' and world == 1 and hasattr(eng, 'model'):
-            # (round 6) the GAT step never runs the plain SpMM: its dominant HBM kernel is the attention-scored aggregation
-            out['roofline'] = dict(time_gat_aggregation(eng), stage_profile=out['roofline']['stage_profile'])
         if note:
             out['config']['partition_fallback'] = note
         out['config']['ranks_seen'] = world          # WORLD_SIZE of the torch.distributed job this line was measured in
+        if world > 1:
+            out['config']['halo_exchanges'] = ('overlapped with compute (the probe reproduced the synchronous result)' if getattr(args, 'dist_overlap', None)
+                                               else f'synchronous ({overlap_note})')
+        if partitioned:
+            out['config']['halo'] = eng.halo_report()
+            out['config']['collective_backend'] = backend
+        if not args.full:
+            print(json.dumps(out))
+            if world > 1:
+                dist.destroy_process_group()
+            return
+        kdur_b2b, kbytes = time_dominant_kernel(eng)
+        kdur_ctx = time_dominant_kernel_in_context(eng) if world == 1 else None
+        kdur = kdur_ctx if kdur_ctx else kdur_b2b           # (in the step's context where that can be measured: see the function)
+        achieved = kbytes / kdur / 1e9
+        prof, prof_note = load_stage_profile(args.stage_profile, data.num_nodes, eng.graph.nnz) if world == 1 else ({}, 'N > 1')
+        traffic = prof.get('stages', {}).get('spmm1', {}).get('traffic_bytes')
+        ceil_ = fabric_ceiling(data.num_nodes, eng.graph.nnz, 128)
+        out['roofline'] = {'kernel': 'spmm_persist_kernel<32,1,4,true,true> (layer-1 CSR SpMM, d=128)', 'bound': 'hbm',
+                           'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
+                           'traffic': traffic,
+                           # the recorded L2-miss (fabric) bytes over this run's launch duration: how close the kernel
+                           # runs to the ~6.3 TB/s a streaming copy achieves on this part (MI355X_MICROARCH.md)
+                           'traffic_gbs': traffic / kdur / 1e9 if traffic else None,
+                           'traffic_unit': ('bytes/launch (PMC FETCH_SIZE x2 + WRITE_SIZE, separate --pmc passes of this command: '
+                                            + os.path.relpath(args.stage_profile, ROOT) + ')') if prof else None,
+                           'stage_profile': os.path.relpath(args.stage_profile, ROOT) if prof else prof_note,
+                           'algorithmic_bytes': kbytes, 'avg_us': kdur * 1e6,
+                           'timing': ('HIP events around 20 (x W1^T; SpMM) pairs minus 20 x W1^T alone: the launch behind the kernel that '
+                                      'precedes it in the step' if kdur_ctx else 'HIP events around 20 back-to-back launches'),
+                           'back_to_back_us': kdur_b2b * 1e6, 'frac_back_to_back': kbytes / kdur_b2b / 1e9 / HBM_PEAK_GBS,
+                           'in_step_us': prof.get('stages', {}).get('spmm1', {}).get('in_step_us'),
+                           # what any kernel with one contiguous row range per XCD can reach on this graph (measurement):
+                           # the private L2s make the fabric carry every x row once per XCD that gathers it
+                           'ceiling_frac_on_this_graph': ceil_['frac'] if ceil_ else None, 'ceiling': ceil_}
+        if args.gnn == 'gat' and world == 1 and hasattr(eng, 'model'):
+            # (round 6) the GAT step never runs the plain SpMM: its dominant HBM kernel is the attention-scored aggregation
+            out['roofline'] = dict(time_gat_aggregation(eng), stage_profile=out['roofline']['stage_profile'])
         if auto_est is not None:
             out['config']['parallel_auto'] = auto_est
             try:        # the whole curve's model from this one run (halo bytes and predicted step at N = 2 / 4 / 8)
                 out['config']['planner_curve'] = planner_curve(eng, auto_est['single_gpu_step_us'], l1_share=auto_est['layer1_share_of_step'])
             except Exception as e:                                   # noqa: BLE001
                 out['config']['planner_curve'] = f'unavailable: {type(e).__name__}: {str(e)[:120]}'
-        if world > 1:
-            out['config']['halo_exchanges'] = ('overlapped with compute (the probe reproduced the synchronous result)' if getattr(args, 'dist_overlap', None)
-                                               else f'synchronous ({overlap_note})')
         if partitioned:
-            # rank 0's own figures + every rank's bytes (gathered over the control group): xGMI is point-to-point, the
+            # rank 0's own figures (above) + every rank's bytes (gathered over the control group): xGMI is point-to-point, the
             # heaviest rank / pair bounds an exchange
-            rep = eng.halo_report()
-            out['config']['halo'] = rep
             out['config']['halo_recv_send_bytes_per_rank'] = per_rank_halo
-            out['config']['collective_backend'] = backend
         if world == 1 and not args.no_cached_rate:
             # informational only (never `value`): the same step with the loop-invariant frozen layer-1
             # output computed once, which is how the trainer runs by default

@@ -11,6 +11,13 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _gpu_visible():
+    import torch
+    return torch.cuda.is_available()
+
+
+@pytest.mark.skipif(_gpu_visible(), reason='host ASAN runs on a machine without a GPU: with a device present the HIP runtime allocates its '
+                                           'device memory pools under the ASAN interceptors, which fail them (out of memory)')
 @pytest.mark.skipif(os.environ.get('GNNDELETE_HIP_LIB') is not None, reason='already running against an alternative library')
 @pytest.mark.skipif(shutil.which('make') is None or not os.path.exists('/opt/rocm/bin/hipcc'), reason='needs make + hipcc')
 def test_layout_suite_passes_under_host_asan():

@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ['--workload', 'synth-small', '--steps', '8', '--warmup', '2', '--pretrain_epochs', '3', '--no_cpu_baseline',
          '--no_cached_rate']
+FULL = SMALL + ['--full']          # roofline, extras, replicas rate, planner estimate and halo bytes are measured only under --full
 
 
 def _json_line(out):
@@ -24,7 +25,7 @@ def _json_line(out):
 
 
 def test_bench_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + SMALL + ['--cpu_baseline_iters', '2'], cwd=ROOT,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + FULL + ['--cpu_baseline_iters', '2'], cwd=ROOT,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = _json_line(r.stdout)
@@ -34,6 +35,33 @@ def test_bench_single_gpu_line():
     assert {'roofline_del_gemm', 'roofline_wgrad', 'roofline_spmm_d64'} <= set(d['extras'])
 
 
+def test_bench_plain_line_is_the_headline_and_dumps_the_same_outputs_twice(tmp_path):
+    """Without --full the line carries the headline only - one region of exactly --steps steps, nothing measured beyond it -
+    and --dump-outputs writes what the timed steps computed; two runs with the same arguments start from identical inputs."""
+    import numpy as np
+    plain = ['--workload', 'synth-small', '--steps', '8', '--warmup', '2', '--pretrain_epochs', '3']
+    dumps = []
+    for run in ('a', 'b'):
+        out_dir = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + plain + ['--dump-outputs', str(out_dir)], cwd=ROOT,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        d = _json_line(r.stdout)
+        assert d['metric'] == 'Del-op train iters/sec' and d['unit'] == 'iters/s' and d['higher_is_better'] is True and d['dtype'] == 'f32'
+        assert d['steps'] == 8 and d['timing']['regions'] == 1 and d['timing']['steps_per_region'] == 8
+        assert abs(d['value'] - 1e3 / d['ms_per_step']) < 1e-6 * d['value']
+        assert not {'roofline', 'extras', 'cpu_baseline', 'post_delete_auc', 'speedup_vs_cpu'} & set(d), sorted(d)
+        got = {name: np.load(out_dir / f'{name}.npy') for name in ('W_D1', 'W_D2', 'loss_last_step')}
+        assert got['W_D1'].dtype == np.float32 and got['W_D1'].shape == (128, 128) and got['W_D2'].shape == (64, 64)
+        assert got['loss_last_step'].dtype == np.float64 and got['loss_last_step'].shape == (3,)
+        assert np.isfinite(got['W_D1']).all() and np.isfinite(got['W_D2']).all() and np.isfinite(got['loss_last_step'][0])
+        assert abs(got['loss_last_step'][0] - d['final_loss']) <= 1e-12 * abs(d['final_loss'])
+        assert not np.allclose(got['W_D1'], 1e-3)          # the Del weights moved off their initial value
+        dumps.append(got)
+    for name in dumps[0]:
+        np.testing.assert_allclose(dumps[1][name], dumps[0][name], rtol=1e-5, atol=1e-9, err_msg=name)
+
+
 @pytest.mark.parametrize('probe', ['0', '1'])
 def test_bench_two_ranks_run_the_partitioned_step(probe):
     """probe = 1 (+ GD_DIST_OVERLAP=1, the request for the overlapped program): both child-process self-tests run first - the
@@ -41,7 +69,7 @@ def test_bench_two_ranks_run_the_partitioned_step(probe):
     exchanges under compute when the second one passed, synchronously with the reason in the line when it did not."""
     env = dict(os.environ, GD_BENCH_BACKEND='gloo', GD_BENCH_FORCE_PROBE=probe, HSA_ENABLE_IPC_MODE_LEGACY='0', GD_DIST_OVERLAP=probe)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-           '--master-port', str(free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--parallel', 'partition'] + SMALL
+           '--master-port', str(free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--parallel', 'partition'] + FULL
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     d = _json_line(r.stdout)
@@ -63,7 +91,7 @@ def test_bench_launches_its_own_ranks_and_auto_keeps_the_partitioned_headline():
     replicas rate and the estimate are reported next to it (a curve must not mix strong- and weak-scaling points)."""
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(GD_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2'] + SMALL, cwd=ROOT, env=env, capture_output=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2'] + FULL, cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert 'launching 2 ranks' in r.stderr
@@ -87,7 +115,7 @@ def test_bench_node_deletion_workload_line():
     the node-classification stand-in (out_dim = #classes = 4, padded inside the engine), the JSON contract with roofline,
     cpu_baseline (the oracle's epoch loop) and HIP-vs-oracle parity after the same iterations."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'synth-small-nodecls', '--gnn', 'gat', '--steps', '8',
-                        '--warmup', '2', '--cpu_baseline_iters', '3'], cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        '--warmup', '2', '--cpu_baseline_iters', '3', '--full'], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = _json_line(r.stdout)
     assert d['n_gpus'] == 1 and d['unit'] == 'iters/s' and d['dtype'] == 'f32' and d['value'] > 0 and d['vs_baseline'] is None
@@ -115,7 +143,7 @@ def test_bench_eight_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(GD_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0', OMP_NUM_THREADS='4')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--parallel', 'partition', '--workload', 'synth-small',
-                        '--steps', '4', '--warmup', '1', '--pretrain_epochs', '0', '--no_cpu_baseline', '--no_cached_rate'], cwd=ROOT, env=env,
+                        '--steps', '4', '--warmup', '1', '--pretrain_epochs', '0', '--no_cpu_baseline', '--no_cached_rate', '--full'], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     d = _json_line(r.stdout)
@@ -129,7 +157,7 @@ def test_bench_two_ranks_partition_the_rgcn_request():
     env = dict(os.environ, GD_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--parallel', 'partition', '--gnn', 'rgcn', '--workload',
-           'synth-kg-small', '--df_size', '2.5', '--steps', '6', '--warmup', '2', '--no_cpu_baseline']
+           'synth-kg-small', '--df_size', '2.5', '--steps', '6', '--warmup', '2', '--no_cpu_baseline', '--full']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     d = _json_line(r.stdout)

@@ -353,13 +353,16 @@ def test_padded_class_dimension_is_exact_in_the_oracle_arithmetic(gnn):
     x = torch.randn(n, h).clamp(min=0)                       # relu(z1)
 
     def conv2(c):
+        # in float64, rounded to float32 at the end: the padded and the unpadded conv are GEMMs of different shapes, whose fp32
+        # summation order depends on the host's BLAS (a CPU with other vector units rounds the two differently)
+        d = torch.Tensor.double
         if gnn == 'gcn':
-            return pyg.gcn_conv(x, ei, c.lin.weight, c.bias)
+            return pyg.gcn_conv(d(x), ei, d(c.lin.weight), d(c.bias)).float()
         if gnn == 'gat':
-            return pyg.gat_conv(x, ei, c.lin_src.weight, c.att_src, c.att_dst, c.bias, c.negative_slope)
+            return pyg.gat_conv(d(x), ei, d(c.lin_src.weight), d(c.att_src), d(c.att_dst), d(c.bias), c.negative_slope).float()
         if gnn == 'gin':
-            return pyg.gin_conv(x, ei, c.nn.weight, c.nn.bias, c.eps)
-        return pyg.sage_conv(x, ei, c.lin_l.weight, c.lin_l.bias, c.lin_r.weight)
+            return pyg.gin_conv(d(x), ei, d(c.nn.weight), d(c.nn.bias), c.eps).float()
+        return pyg.sage_conv(d(x), ei, d(c.lin_l.weight), d(c.lin_l.bias), d(c.lin_r.weight)).float()
     with torch.no_grad():
         want, got = conv2(model.conv2), conv2(sh.conv2)
         assert got.shape == (n, pad) and float(got[:, o:].abs().max()) == 0.0
@@ -374,3 +377,21 @@ def test_padded_class_dimension_is_exact_in_the_oracle_arithmetic(gnn):
         dz2[:, :o] = torch.randn(n, o)
         gw = got[m2].t() @ dz2[m2]
         assert float(gw[o:].abs().max()) == 0.0 and float(gw[:, o:].abs().max()) == 0.0
+
+
+def test_bench_options_full_and_dump_outputs(monkeypatch):
+    """bench.py's command line (host logic, no GPU): --full is off by default, --dump-outputs names a directory, and a plain run
+    times one region of exactly --steps steps (--full keeps five regions below 100 steps; --repeats overrides both)."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5'])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 20 and a.warmup == 5
+    assert bench.timed_regions(a) == 1
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '20', '--full', '--dump-outputs', 'outs'])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == 'outs' and bench.timed_regions(a) == 5
+    a.steps = 200
+    assert bench.timed_regions(a) == 1
+    a.repeats = 3
+    assert bench.timed_regions(a) == 3

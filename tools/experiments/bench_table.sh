@@ -1,6 +1,6 @@
 # the it/s table of DESIGN.md section 7: every model on synth-collab, GCN/GAT/GIN on the two small stand-ins
 cd $GRAFT_REPO_ROOT
-run() { python bench.py "$@" --no_cpu_baseline 2>/dev/null | python -c "
+run() { python bench.py "$@" --full --no_cpu_baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1])
 print(d['config']['workload'][:60], '|', round(d['value'], 1), 'it/s |', round(d['ms_per_step'], 3), 'ms | cached',
