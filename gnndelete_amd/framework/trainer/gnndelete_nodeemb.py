@@ -287,6 +287,14 @@ class GNNDeleteNodeembTrainer(_EmbeddingUnlearner, Trainer):
         its GPUs together with the N x N bookkeeping (gnndelete_nodeemb.py:352-495).  On MI355X the
         whole graph is one batch; see .sampler for the mini-batch loop kept for parity studies."""
         from .sampler import train_minibatch
+        if getattr(args, 'fused_minibatch', False):
+            from ...minibatch import fused_minibatch_unsupported, train_minibatch_fused
+            reason = fused_minibatch_unsupported(model, args, optimizer)
+            if reason is None:
+                self.trainer_log['minibatch_step'] = 'fused'
+                return train_minibatch_fused(self, model, data, optimizer, args)
+            print(f'--fused_minibatch: {reason}; running the autograd mini-batch loop', flush=True)
+        self.trainer_log['minibatch_step'] = 'autograd'
         return train_minibatch(self, model, data, optimizer, args)
 
 

@@ -1,0 +1,444 @@
+"""GraphSAINT mini-batch unlearning on a fused HIP batch step (--minibatch --fused_minibatch).
+
+The reference trains the Del operators of ogbl-* graphs on GraphSAINT random-walk batches
+(framework/trainer/gnndelete_nodeemb.py:352-445); framework.trainer.sampler.train_minibatch runs that loop through
+autograd.  NodeembEngine cannot serve it: it is built once per request (locality order, split plans, fp64-folded loss
+terms, a captured graph) while a batch changes the graph, the masks, the loss rows and the sizes on every step.
+MinibatchNodeembStep is the same idea for shapes that change per batch - an explicit forward, a hand-derived backward
+and Adam on the HIP kernels, fed by a device-side subgraph cut:
+
+  1. gd_induced_subgraph: the batch's edges (relabelled, in subgraph() order), its Df edges, its S1 / S2 / NI1 / NI2
+     rows and a count vector - the ONE blocking host read of a batch (outside negative_sampling);
+  2. gd_batch_csr: the CSRs over all batch edges (z_ori) and over its sdf edges (Del forward / backward), index arrays
+     as graph.build_csr makes them, without SplitPlans (the plain per-row kernels fit batch sizes);
+  3. frozen layer 1: x W1^T (and GAT's attention scores) is computed ONCE per run for the whole graph and gathered per
+     batch, then aggregated over each batch CSR (gd_spmm_csr_f32 / gd_gat_aggregate_f32);
+  4. layer 2, both Del operators, negatives (sampler.negative_sampling, the tests' seam), DEC + NI of both layers
+     (gd_batch_loss_terms + gd_rowpair_mse_f32: deterministic per-row segments), the layer-wise backward and Adam.
+
+Update order is the autograd loop's: loss1's gradient -> Adam on W_D1; loss2's gradient (W_D2's, and W_D1's, which is
+kept and added to the next batch's W_D1 gradient) -> Adam on W_D2.  The per-step losses stay on the device and become
+trainer_log['steps'] once per epoch."""
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from ._lib import check, ptr, stream_ptr
+
+N_COUNTS = 11          # gd_induced_subgraph's count vector
+
+
+def fused_minibatch_unsupported(model, args, optimizer):
+    """None when the fused batch step applies, else the reason it does not (one line)."""
+    from .framework.trainer.sampler import data_parallel_world
+    from .nn import GATConv, GCNConv
+    conv1, conv2 = getattr(model, 'conv1', None), getattr(model, 'conv2', None)
+    if not (isinstance(conv1, (GCNConv, GATConv)) and type(conv1) is type(conv2)) or not hasattr(model, 'deletion1'):
+        return f'no fused batch step for the {type(model).__name__} backbone (GCN and GAT only)'
+    if getattr(args, 'loss_fct', 'mse_mean') not in ('mse_mean', 'mse_sum'):
+        return f'--loss_fct {args.loss_fct} is not an MSE loss'
+    if data_parallel_world()[1] > 1:
+        return 'torch.distributed with more than one rank'
+    opts = list(optimizer) if isinstance(optimizer, (list, tuple)) else [optimizer]
+    for opt in opts:
+        g = opt.param_groups[0]
+        if not isinstance(opt, torch.optim.Adam) or g.get('weight_decay', 0) or g.get('amsgrad') or g.get('maximize'):
+            return 'the optimizer is not a plain torch.optim.Adam'
+    return None
+
+
+def _grow(n):
+    return max(1024, 1 << int(np.ceil(np.log2(max(n, 1) * 1.25))))
+
+
+class _BatchCSR:
+    __slots__ = ('n', 'nnz', 'rowptr', 'col', 'val', 'rowptr_t', 'col_t', 'perm_t', 'val_t')
+
+
+class BatchCut:
+    """The device side of a GraphSAINT batch: the sampler's source-major CSR and flag bytes (packed once per run), the
+    node-sized relabel array, and buffers for the cut's outputs (node buffers sized to the batch upper bound, edge
+    buffers grown geometrically when a cut reports more)."""
+
+    def __init__(self, data, loader, dev, max_nodes=None):
+        self.dev = dev
+        self.n = int(loader.n)
+        # the sampler's source-major CSR (sorted by (src, dst), stable ties) and one flag byte per edge in that order
+        self.rowptr32 = loader.rowptr.to(device=dev, dtype=torch.int32).contiguous()
+        self.col32 = loader.dst_sorted.to(device=dev, dtype=torch.int32).contiguous()
+        order = loader.order.to(data.sdf_mask.device)
+        flags = data.sdf_mask.to(torch.uint8) | (data.df_mask.to(torch.uint8) << 1)
+        self.edge_flags = flags[order].to(dev).contiguous()
+        node_flags = torch.zeros(self.n, dtype=torch.uint8)
+        for bit, key in enumerate(['sdf_node_1hop_mask', 'sdf_node_2hop_mask', 'sdf_node_1hop_mask_non_df_mask',
+                                   'sdf_node_2hop_mask_non_df_mask']):
+            node_flags |= getattr(data, key).to('cpu', torch.uint8) << bit
+        self.node_flags = node_flags.to(dev)
+        self.relabel = torch.zeros(self.n, dtype=torch.int64, device=dev)
+        self.generation = 0
+        self.counts = torch.zeros(N_COUNTS, dtype=torch.int32, device=dev)
+        self.n_cap = self.e_cap = 0
+        self._bufs = {}
+        self._ensure(max_nodes or 1024, 4 * (max_nodes or 1024))
+        self.reads = 0                  # blocking host reads made by the cut (the count vector)
+
+    # ---------------------------------------------------------------------------------------------- buffers
+    def _ensure(self, n_b, e):
+        if n_b <= self.n_cap and e <= self.e_cap:
+            return
+        self.n_cap, self.e_cap = max(self.n_cap, _grow(n_b)), max(self.e_cap, _grow(e))
+        dev, n, c = self.dev, self.n_cap, self.e_cap
+        i64 = dict(dtype=torch.int64, device=dev)
+        self.e_index = torch.empty(2, c, **i64)
+        self.e_flags = torch.empty(c, dtype=torch.uint8, device=dev)
+        self.all_src, self.all_dst = torch.empty(c + n, **i64), torch.empty(c + n, **i64)
+        self.sdf_src, self.sdf_dst = torch.empty(c + n, **i64), torch.empty(c + n, **i64)
+        self.df_index = torch.empty(2, c, **i64)
+        self.row_lists = torch.empty(4 * n, dtype=torch.int32, device=dev)     # list k at k * n_b
+        self.seg_row = torch.arange(n, dtype=torch.int32, device=dev)
+
+    def _ws(self, key, nbytes):
+        if nbytes < 0:
+            raise ValueError(f'{key}: batch too large for int32 indices')
+        buf = self._bufs.get(key)
+        if buf is None or buf.numel() < nbytes:
+            buf = self._bufs[key] = torch.empty(max(256, _grow(nbytes)), dtype=torch.uint8, device=self.dev)
+        return buf
+
+    # ---------------------------------------------------------------------------------------------- the cut
+    def cut(self, nodes):
+        """gd_induced_subgraph on one sorted, unique node set -> the host copy of the count vector."""
+        nodes = nodes.to(self.dev, torch.int64).contiguous()
+        n_b = int(nodes.numel())
+        self._ensure(n_b, 0)
+        self.generation += 1
+        L = _lib.lib()
+        while True:
+            ws = self._ws('cut', L.gd_induced_subgraph_workspace(n_b))
+            check(L.gd_induced_subgraph(ptr(self.rowptr32), ptr(self.col32), ptr(self.edge_flags), self.n, ptr(nodes), n_b,
+                                        ptr(self.node_flags), self.generation, ptr(self.relabel), self.e_cap,
+                                        ptr(self.e_index), ptr(self.e_flags), ptr(self.all_src), ptr(self.all_dst),
+                                        ptr(self.sdf_src), ptr(self.sdf_dst), ptr(self.df_index), ptr(self.row_lists),
+                                        ptr(self.counts), ptr(ws), ws.numel(), stream_ptr(self.dev)), 'gd_induced_subgraph')
+            cnt = self.counts.tolist()
+            self.reads += 1
+            if cnt[1] <= self.e_cap:
+                break
+            self._ensure(n_b, cnt[1])                      # the edge outputs were not written: grow, cut again
+        if cnt[10]:
+            raise IndexError(f'batch node ids outside [0, {self.n})')
+        self.nodes, self.cnt = nodes, cnt
+        return cnt
+
+    def rows(self, k, count):
+        """Batch rows of the latest cut with node flag bit k (0 S1, 1 S2, 2 NI1, 3 NI2), ascending: int32 [count]."""
+        n_b = self.cnt[0]
+        return self.row_lists.view(-1)[k * n_b:k * n_b + count]
+
+    def batch_edges(self):
+        """(edge_index [2, e_all] int64, flags [e_all] uint8) of the latest cut, views of the step's buffers."""
+        e = self.cnt[1]
+        return self.e_index[:, :e], self.e_flags[:e]
+
+    def batch_csr(self, sdf, gat):
+        """gd_batch_csr over the latest cut's sdf edges (sdf=True) or all its edges; gcn values unless gat."""
+        n_b = self.cnt[0]
+        n_e = self.cnt[9] if sdf else self.cnt[8]
+        src, dst = (self.sdf_src, self.sdf_dst) if sdf else (self.all_src, self.all_dst)
+        g = _BatchCSR()
+        g.n, g.nnz = n_b, n_e + n_b
+        i32 = dict(dtype=torch.int32, device=self.dev)
+        g.rowptr, g.rowptr_t = torch.empty(n_b + 1, **i32), torch.empty(n_b + 1, **i32)
+        g.col, g.col_t, g.perm_t = torch.empty(g.nnz, **i32), torch.empty(g.nnz, **i32), torch.empty(g.nnz, **i32)
+        g.val = g.val_t = None
+        if not gat:
+            g.val = torch.empty(g.nnz, dtype=torch.float32, device=self.dev)
+            g.val_t = torch.empty(g.nnz, dtype=torch.float32, device=self.dev)
+        L = _lib.lib()
+        ws = self._ws('csr', L.gd_batch_csr_workspace(n_b, n_e))
+        check(L.gd_batch_csr(ptr(src), ptr(dst), n_e, n_b, 1 if gat else 0, ptr(g.rowptr), ptr(g.col), ptr(g.val),
+                             ptr(g.rowptr_t), ptr(g.col_t), ptr(g.perm_t), ptr(g.val_t), ptr(ws), ws.numel(),
+                             stream_ptr(self.dev)), 'gd_batch_csr')
+        return g
+
+class MinibatchNodeembStep:
+    """Owns the per-run state of the fused batch step: a BatchCut, the frozen layer-1 transform of every node, the
+    Adam moments and the carried W_D1 gradient."""
+
+    def __init__(self, model, data, loader, alpha, lr, betas, eps, max_nodes=None):
+        from .nn import GATConv
+        dev = next(model.parameters()).device
+        self.dev, self.model, self.alpha = dev, model, float(alpha)
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.gat = isinstance(model.conv1, GATConv)
+        self.cut = BatchCut(data, loader, dev, max_nodes)
+        # frozen layer 1: the feature transform (and GAT's scores) of every node, once
+        c1, c2 = model.conv1, model.conv2
+        lin1 = c1.lin_src if self.gat else c1.lin
+        lin2 = c2.lin_src if self.gat else c2.lin
+        with torch.no_grad():
+            x = data.x.to(dev, torch.float32)
+            self.h1_all = ops.dense(x, lin1.weight.detach(), None, True).contiguous()
+            if self.gat:
+                a_s, a_d = ops.row_dots(self.h1_all, c1.att_src.detach(), c1.att_dst.detach())
+                self.a1_all = torch.stack([a_s, a_d], 1).contiguous()
+        self.b1, self.b2 = c1.bias.detach().contiguous(), c2.bias.detach().contiguous()
+        self.w2 = lin2.weight.detach().contiguous()                       # [O, H]
+        if self.gat:
+            self.att2 = (c2.att_src.detach().reshape(-1).contiguous(), c2.att_dst.detach().reshape(-1).contiguous())
+            self.slope1, self.slope2 = float(c1.negative_slope), float(c2.negative_slope)
+        self.H, self.O = self.h1_all.shape[1], self.w2.shape[0]
+        # trainable state: the model's own Del weights are stepped in place
+        self.wd1, self.wd2 = model.deletion1.deletion_weight, model.deletion2.deletion_weight
+        self.adam = []
+        for p in (self.wd1, self.wd2):
+            self.adam.append({'m': torch.zeros_like(p.data), 'v': torch.zeros_like(p.data),
+                              'step': torch.zeros(1, dtype=torch.int32, device=dev), 'steps': 0})
+        self.g1 = torch.zeros_like(self.wd1.data)
+        self.g2 = torch.zeros_like(self.wd2.data)
+        self.g1_live = False            # W_D1 holds loss2's gradient of the previous batch (carried into the next step)
+        self._bufs = {}
+        self.events = None              # list -> (stage, cuda event) pairs are appended (stage split of the experiment)
+
+    def _ws(self, key, nbytes):
+        if nbytes < 0:
+            raise ValueError(f'{key}: batch too large for int32 indices')
+        buf = self._bufs.get(key)
+        if buf is None or buf.numel() < nbytes:
+            buf = self._bufs[key] = torch.empty(max(256, _grow(nbytes)), dtype=torch.uint8, device=self.dev)
+        return buf
+
+    def _mark(self, stage):
+        if self.events is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self.events.append((stage, ev))
+
+    # ---------------------------------------------------------------------------------------------- layers
+    def _agg(self, g, h, scores, bias, slope):
+        """GCNConv / GATConv aggregation of transformed rows h over a batch CSR -> (y, saved attention or None)."""
+        y = torch.empty(g.n, h.shape[1], dtype=torch.float32, device=self.dev)
+        if not self.gat:
+            check(_lib.lib().gd_spmm_csr_f32(ptr(g.rowptr), ptr(g.col), ptr(g.val), ptr(h), h.stride(0), ptr(y), y.stride(0),
+                                             ptr(bias), 0.0, g.n, h.shape[1], stream_ptr(self.dev)), 'gd_spmm_csr_f32')
+            return y, None
+        a_src, a_dst = scores
+        alpha = torch.empty(g.nnz, dtype=torch.float32, device=self.dev)
+        check(_lib.lib().gd_gat_aggregate_f32(ptr(g.rowptr), ptr(g.col), ptr(a_src), ptr(a_dst), ptr(h), h.stride(0), ptr(y),
+                                              y.stride(0), ptr(bias), ptr(alpha), float(slope), g.n, h.shape[1],
+                                              stream_ptr(self.dev)), 'gd_gat_aggregate_f32')
+        return y, alpha
+
+    def _agg_bwd(self, g, h, scores, alpha, dy, slope, att):
+        """Input gradient of _agg with respect to h (GAT: message path + the score terms' rank-1 rows)."""
+        n, d = g.n, dy.shape[1]
+        if not self.gat:
+            dh = torch.empty(n, d, dtype=torch.float32, device=self.dev)
+            check(_lib.lib().gd_spmm_csr_f32(ptr(g.rowptr_t), ptr(g.col_t), ptr(g.val_t), ptr(dy), dy.stride(0), ptr(dh),
+                                             dh.stride(0), None, 0.0, n, d, stream_ptr(self.dev)), 'gd_spmm_csr_f32')
+            return dh
+        a_src, a_dst = scores
+        dh = torch.empty(n, d, dtype=torch.float32, device=self.dev)
+        da = torch.empty(2, n, dtype=torch.float32, device=self.dev)
+        de = torch.empty(g.nnz, dtype=torch.float32, device=self.dev)
+        check(_lib.lib().gd_gat_aggregate_bwd_f32(ptr(g.rowptr), ptr(g.col), ptr(alpha), ptr(g.rowptr_t), ptr(g.col_t),
+                                                  ptr(g.perm_t), ptr(a_src), ptr(a_dst), ptr(h), h.stride(0), ptr(dy),
+                                                  dy.stride(0), ptr(dh), dh.stride(0), ptr(da[0]), ptr(da[1]), ptr(de),
+                                                  float(slope), n, d, stream_ptr(self.dev)), 'gd_gat_aggregate_bwd_f32')
+        return ops.rank1_add2_(dh, da[0], att[0], da[1], att[1])
+
+    def _layer2(self, g, z1):
+        """conv2(relu(z1)) over g -> (y, h, scores, saved attention)."""
+        h = ops.rows_gemm(z1, None, self.w2, trans_w=True, relu_in=True)
+        scores = ops.row_dots(h, *self.att2) if self.gat else None
+        y, alpha = self._agg(g, h, scores, self.b2, self.slope2 if self.gat else 0.0)
+        return y, h, scores, alpha
+
+    def _loss(self, z, z_ori, neg, n_pos, ni, n_ni, d, sums):
+        """DEC + NI of one layer: sums[0] += sum of squared DEC differences, sums[1] += NI's; -> dz of alpha * DEC_mean +
+        (1 - alpha) * NI_mean (a mean over zero rows has no gradient)."""
+        L = _lib.lib()
+        c = self.cut
+        n_b = c.cnt[0]
+        n_terms = 2 * n_pos + n_ni
+        w_dec = self.alpha / (2 * n_pos * d) if n_pos else 0.0
+        w_ni = (1.0 - self.alpha) / (n_ni * d) if n_ni else 0.0
+        seg_ptr = torch.empty(n_b + 1, dtype=torch.int32, device=self.dev)
+        term_o = torch.empty(max(n_terms, 1), dtype=torch.int32, device=self.dev)
+        term_w = torch.empty(max(n_terms, 1), dtype=torch.float32, device=self.dev)
+        term_kind = torch.empty(max(n_terms, 1), dtype=torch.int32, device=self.dev)
+        ws = self._ws('terms', L.gd_batch_loss_terms_workspace(n_b, n_terms))
+        check(L.gd_batch_loss_terms(ptr(c.df_index), c.e_cap, ptr(neg), neg.stride(0), n_pos, ptr(ni), n_ni, n_b, w_dec,
+                                    w_ni, ptr(seg_ptr), ptr(term_o), ptr(term_w), ptr(term_kind), ptr(ws), ws.numel(),
+                                    stream_ptr(self.dev)), 'gd_batch_loss_terms')
+        dz = torch.empty(n_b, d, dtype=torch.float32, device=self.dev)
+        part = torch.empty(max(1, L.gd_rowpair_mse_workspace(n_b)), dtype=torch.float32, device=self.dev)
+        check(L.gd_rowpair_mse_f32(ptr(z), z.stride(0), ptr(z_ori), z_ori.stride(0), d, ptr(seg_ptr), ptr(c.seg_row), n_b,
+                                   ptr(term_o), ptr(term_w), ptr(term_kind), ptr(dz), dz.stride(0), 0, ptr(sums), ptr(part),
+                                   stream_ptr(self.dev)), 'gd_rowpair_mse_f32')
+        return dz
+
+    def _adam(self, k, p, grad):
+        st = self.adam[k]
+        check(_lib.lib().gd_adam_f32(ptr(p.data), ptr(grad), ptr(st['m']), ptr(st['v']), ptr(st['step']), p.numel(), self.lr,
+                                     self.betas[0], self.betas[1], self.eps, stream_ptr(self.dev)), 'gd_adam_f32')
+        st['steps'] += 1
+
+    # ---------------------------------------------------------------------------------------------- one batch
+    def step(self, nodes, sums):
+        """One batch of the layer-wise update on `nodes`; sums [4] (zeroed by the caller) receives the squared-difference
+        sums (DEC 1, NI 1, DEC 2, NI 2).  Returns the divisors that turn them into the four means."""
+        from .framework.trainer import sampler as S
+        self._mark('start')
+        c = self.cut
+        cnt = c.cut(nodes)
+        n_b, m_df, n_s1, n_s2, n_ni1, n_ni2 = cnt[0], cnt[3], cnt[4], cnt[5], cnt[6], cnt[7]
+        self._mark('cut')
+        g_all, g_sdf = c.batch_csr(False, self.gat), c.batch_csr(True, self.gat)
+        self._mark('csr')
+        H, O = self.H, self.O
+        idx1, idx2, ni1, ni2 = (c.rows(k, cnt) for k, cnt in enumerate((n_s1, n_s2, n_ni1, n_ni2)))
+        # frozen layer 1 on both graphs (x W1^T and the GAT scores gathered from the per-run table)
+        h1 = self.h1_all.index_select(0, c.nodes)
+        sc1 = None
+        if self.gat:
+            a1 = self.a1_all.index_select(0, c.nodes)
+            sc1 = (a1[:, 0].contiguous(), a1[:, 1].contiguous())
+        z1_ori, _ = self._agg(g_all, h1, sc1, self.b1, self.slope1 if self.gat else 0.0)
+        p1, _ = self._agg(g_sdf, h1, sc1, self.b1, self.slope1 if self.gat else 0.0)
+        z2_ori = self._layer2(g_all, z1_ori)[0]
+        # Del forward on the sdf graph
+        wd1, wd2 = self.wd1.data, self.wd2.data
+        z1 = p1.clone()
+        if n_s1:
+            ops.rows_gemm(p1, idx1, wd1, out=z1)
+        p2, h2, sc2, alpha2 = self._layer2(g_sdf, z1)
+        z2 = p2.clone()
+        if n_s2:
+            ops.rows_gemm(p2, idx2, wd2, out=z2)
+        self._mark('forward')
+        edge_index, _ = c.batch_edges()
+        neg = S.negative_sampling(edge_index, n_b, m_df).to(self.dev, torch.int64).contiguous()
+        self._mark('negatives')
+        dz1 = self._loss(z1, z1_ori, neg, m_df, ni1, n_ni1, H, sums[0:2])
+        dz2 = self._loss(z2, z2_ori, neg, m_df, ni2, n_ni2, O, sums[2:4])
+        self._mark('loss')
+        # loss1: W_D1's gradient (+ what loss2 left on it last batch), Adam.  torch would skip a parameter whose .grad is
+        # None; the Del layer's autograd node always returns a weight gradient (zeros without S1 rows), so neither
+        # parameter is ever skipped on the autograd path and none is here.
+        if n_s1:
+            ops.rows_gemm_wgrad(p1, idx1, dz1, idx1, n_s1, out=self.g1, accumulate=self.g1_live)
+        elif not self.g1_live:
+            self.g1.zero_()
+        self._adam(0, self.wd1, self.g1)
+        # loss2: W_D2's gradient and, through conv2 and the ReLU, a fresh W_D1 gradient that waits for the next batch
+        if n_s2:
+            ops.rows_gemm_wgrad(p2, idx2, dz2, idx2, n_s2, out=self.g2)
+        else:
+            self.g2.zero_()
+        dp2 = dz2.clone()
+        if n_s2:
+            ops.rows_gemm(dz2, idx2, wd2, trans_w=True, out=dp2)
+        dh2 = self._agg_bwd(g_sdf, h2, sc2, alpha2, dp2, self.slope2 if self.gat else 0.0, self.att2 if self.gat else None)
+        dx1 = ops.rows_gemm(dh2, None, self.w2)                  # [n_b, H], before the ReLU gate
+        if n_s1:
+            ops.rows_gemm_wgrad(p1, idx1, dx1, idx1, n_s1, relu_mask=z1, out=self.g1)
+        else:
+            self.g1.zero_()
+        self.g1_live = True
+        self._adam(1, self.wd2, self.g2)
+        self._mark('backward')
+        return (2 * m_df * H, n_ni1 * H, 2 * m_df * O, n_ni2 * O)
+
+    # ---------------------------------------------------------------------------------------------- optimizer state
+    def import_adam_state(self, optimizer):
+        opts = list(optimizer) if isinstance(optimizer, (list, tuple)) else [optimizer, optimizer]
+        for k, (opt, p) in enumerate(zip(opts, (self.wd1, self.wd2))):
+            st = opt.state.get(p)
+            if st and 'exp_avg' in st:
+                self.adam[k]['m'].copy_(st['exp_avg'])
+                self.adam[k]['v'].copy_(st['exp_avg_sq'])
+                self.adam[k]['steps'] = int(st['step'])
+                self.adam[k]['step'].fill_(self.adam[k]['steps'])
+        if self.wd1.grad is not None:                       # a gradient left on W_D1 joins the first step
+            self.g1.copy_(self.wd1.grad)
+            self.g1_live = True
+
+    def export_adam_state(self, optimizer):
+        """Adam moments and step counts into the caller's torch optimizers (as _export_adam_state does for the
+        full-graph engine); W_D1 keeps loss2's last gradient as .grad, as after the autograd loop."""
+        opts = list(optimizer) if isinstance(optimizer, (list, tuple)) else [optimizer, optimizer]
+        for opt, st, p in zip(opts, self.adam, (self.wd1, self.wd2)):
+            if st['steps']:
+                opt.state[p] = {'step': torch.tensor(float(st['steps'])), 'exp_avg': st['m'].clone(),
+                                'exp_avg_sq': st['v'].clone()}
+        self.wd1.grad = self.g1.clone() if self.g1_live else None
+        self.wd2.grad = None
+
+
+def _step_log(epoch, sums, div, alpha):
+    """The autograd loop's step log from the four squared-difference sums (fp32 means, as MSELoss computes them)."""
+    f = np.float32
+    with np.errstate(divide='ignore', invalid='ignore'):
+        r1, l1, r2, l2 = (f(s) / f(d) for s, d in zip(sums, div))
+        loss1 = f(alpha) * r1 + f(1 - alpha) * l1
+        loss2 = f(alpha) * r2 + f(1 - alpha) * l2
+        return {'Epoch': epoch, 'train_loss': float(loss1 + loss2), 'train_loss_l': float(l1 + l2),
+                'train_loss_r': float(r1 + r2)}
+
+
+def train_minibatch_fused(trainer, model, data, optimizer, args, step_hook=None):
+    """framework.trainer.sampler.train_minibatch with the batch step on the HIP kernels: same sampler and negatives
+    (same random stream), same update order, logs, validation and checkpoints."""
+    from .framework.trainer import sampler as S
+    from .framework.trainer._log import wandb_log
+    from .framework.trainer.base import _require_gpu, device
+    from .framework.trainer.gnndelete_nodeemb import _adam_hyper, _non_df_masks
+    _require_gpu()
+    data = data.to('cpu')
+    _non_df_masks(data)
+    data.edge_index = data.train_pos_edge_index
+    data.node_id = torch.arange(data.x.shape[0])
+    loader = S.make_sampler(data, args.batch_size, args.num_steps)
+    model = model.to(device)
+    lr, betas, eps = _adam_hyper(optimizer)
+    step = MinibatchNodeembStep(model, data, loader, trainer.args.alpha, lr, betas, eps,
+                                max_nodes=(loader.walk_length + 1) * max(int(loader.batch_size), 1))
+    step.import_adam_state(optimizer)
+    trainer._fused_minibatch_step = step
+    best_metric = 0
+    trainer.trainer_log['steps'] = []
+    for epoch in range(args.epochs):
+        model.train()
+        hist = torch.zeros(max(len(loader), 1), 4, dtype=torch.float32, device=device)
+        divs = []
+        for i, nodes in enumerate(loader.node_sets()):
+            if i >= hist.shape[0]:
+                hist = torch.cat([hist, torch.zeros_like(hist)])
+            divs.append(step.step(nodes, hist[i]))
+            if step_hook is not None:
+                step_hook(step)
+        sums = {'loss': 0.0, 'loss_l': 0.0, 'loss_r': 0.0}
+        for s4, div in zip(hist[:len(divs)].tolist(), divs):
+            step_log = _step_log(epoch, s4, div, trainer.args.alpha)
+            wandb_log(step_log)
+            trainer.trainer_log['steps'].append(step_log)
+            sums['loss'] += step_log['train_loss']
+            sums['loss_l'] += step_log['train_loss_l']
+            sums['loss_r'] += step_log['train_loss_r']
+        steps = len(divs)
+        if (epoch + 1) % args.valid_freq == 0:
+            valid_loss, dt_auc, dt_aup, df_auc, df_aup, df_logit, _, valid_log = trainer.eval(model, data, 'val')
+            denom = max(steps - 1, 1)          # upstream divides by the last enumerate index
+            train_log = {'epoch': epoch, 'train_loss': sums['loss'] / denom, 'train_loss_l': sums['loss_l'] / denom,
+                         'train_loss_r': sums['loss_r'] / denom}
+            trainer._record(train_log, valid_log)
+            if dt_auc + df_auc > best_metric:
+                best_metric = dt_auc + df_auc
+                torch.save({'model_state': model.state_dict()}, os.path.join(args.checkpoint_dir, 'model_best.pt'))
+            data = data.to('cpu')
+    step.export_adam_state(optimizer)
+    torch.save({'model_state': {k: v.to('cpu') for k, v in model.state_dict().items()}},
+               os.path.join(args.checkpoint_dir, 'model_final.pt'))

@@ -42,7 +42,8 @@ extern "C" {
                                 gd_typed_edge_dot_f32, gd_spmm_csr_onepass_aux_f32, gd_del1_loss_wgrad_f32; gd_rowtarget_mse_f32 accepts dz = NULL;
                                 gd_agg_gemm_f32 and gd_spmm_csr_rowgroup_f32 removed (opt-in forms nobody defaulted);
                              9: gd_rows_gemm_accumulate_f32; gd_rows_gemm_select_f32 / gd_rows_gemm_dots_f32 run weight-stationary with a selector
-                                AND an index list; the one-launch item kernels abort on a misaligned XCD range table instead of deadlocking */
+                                AND an index list; the one-launch item kernels abort on a misaligned XCD range table instead of deadlocking;
+                                gd_induced_subgraph, gd_batch_csr, gd_batch_loss_terms (+ their _workspace queries): the GraphSAINT batch step */
 
 enum {
   GD_OK = 0,
@@ -699,6 +700,61 @@ int gd_typed_wgrad_f32(const int32_t* rel_ptr, int32_t n_rel, const int32_t* src
 int gd_typed_edge_dot_f32(const int32_t* src, const int32_t* dst, const int32_t* rel, int64_t n_edges, const float* x, int64_t ldx,
                           const float* dy, int64_t ldy, const float* weight, int32_t n_blocks, int32_t d_in, int32_t d_out,
                           float* out, void* stream);
+
+/* ---------------------------------------------------------------- GraphSAINT batches ---- */
+
+/* The induced subgraph of one GraphSAINT batch (torch_geometric saint_subgraph as the reference's mini-batch loop uses it,
+ * framework/trainer/gnndelete_nodeemb.py:379-385; RandomWalkSubgraphSampler.subgraph here), cut on the device.
+ *   rowptr / col  [n_nodes + 1] / [E]: CSR over SOURCE rows of the training edges, edges of a row sorted by target, ties
+ *                 in input order (the sampler's stable (src, dst) sort); edge_flags [E]: one byte per edge in that order,
+ *                 bit 0 = sdf_mask, bit 1 = df_mask
+ *   nodes [n_b]   int64, the batch's node ids, ascending and unique; row r of the batch is nodes[r]
+ *   node_flags    [n_nodes] (optional): bit 0 S1 (sdf_node_1hop_mask), bit 1 S2, bit 2 NI1, bit 3 NI2 (the non-Df masks)
+ *   relabel       [n_nodes] int64, zeroed ONCE by the caller: generation << 32 | batch id of the nodes of the latest cut;
+ *                 `generation` must differ from (and exceed 0 and) every earlier call's on the same array - nothing is cleared
+ *   edge_cap      capacity of the edge outputs.  When the batch has more edges, counts is still written and the edge
+ *                 outputs are not: the caller grows its buffers and cuts again (same generation is fine)
+ * Outputs (device):
+ *   e_index [2, edge_cap] int64 (row 1 at e_index + edge_cap), e_flags [edge_cap]: the induced edges in batch ids, sorted by
+ *           (src, dst) - exactly what subgraph() yields - and their flag bytes
+ *   all_src / all_dst   [edge_cap + n_b] int64: the batch edges without self loops (what graph.build_csr keeps), in that order
+ *   sdf_src / sdf_dst   [edge_cap + n_b] int64: the same for the sdf edges (gd_batch_csr appends the self loops behind them)
+ *   df_index [2, edge_cap] int64: the Df edges (the batch's positive DEC pairs)
+ *   row_lists [4, n_b] int32: batch rows with node flag bit k set, ascending, list k at row_lists + k * n_b
+ *   counts [11] int32: n_b, e_all, e_sdf, m_df, |S1_b|, |S2_b|, |NI1_b|, |NI2_b|, e_all without self loops, e_sdf without
+ *           self loops, and 1 if a node id was outside [0, n_nodes) (such rows are cut as empty)
+ *   workspace >= gd_induced_subgraph_workspace(n_b) bytes, 256-byte aligned.
+ * One wave per batch row; rows of any length (hubs) are walked 64 edges at a time.  Integer only, bit-exact. */
+int64_t gd_induced_subgraph_workspace(int32_t n_b);
+int gd_induced_subgraph(const int32_t* rowptr, const int32_t* col, const uint8_t* edge_flags, int32_t n_nodes,
+                        const int64_t* nodes, int32_t n_b, const uint8_t* node_flags, int32_t generation,
+                        int64_t* relabel, int64_t edge_cap, int64_t* e_index, uint8_t* e_flags, int64_t* all_src,
+                        int64_t* all_dst, int64_t* sdf_src, int64_t* sdf_dst, int64_t* df_index, int32_t* row_lists,
+                        int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* graph.build_csr(edge_index, n_nodes, mode) for a batch, without a host round trip: src / dst hold n_edges edges without
+ * self loops and room for n_nodes more, where the self loops are appended (in place).  Writes the target-major CSR
+ * (rowptr [n+1], col [nnz]), the source-major one (rowptr_t, col_t), perm_t [nnz] (forward slot of every transposed entry)
+ * and, for mode 0 (gcn), val / val_t (gd_gcn_norm_f32); mode 1 (gat) leaves val / val_t alone (may be NULL).
+ * nnz = n_edges + n_nodes.  The index arrays are those build_csr computes from the same edge list (gd_csr_from_coo).
+ * workspace >= gd_batch_csr_workspace(n_nodes, n_edges) bytes, 256-byte aligned. */
+int64_t gd_batch_csr_workspace(int32_t n_nodes, int64_t n_edges);
+int gd_batch_csr(int64_t* src, int64_t* dst, int64_t n_edges, int32_t n_nodes, int32_t mode, int32_t* rowptr, int32_t* col,
+                 float* val, int32_t* rowptr_t, int32_t* col_t, int32_t* perm_t, float* val_t, void* workspace,
+                 int64_t workspace_bytes, void* stream);
+
+/* The segmented inputs of gd_rowpair_mse_f32 for one layer of a batch (targets change every batch, so the pre-folded
+ * gd_rowtarget_mse_f32 form does not apply): DEC terms (z row pos[0][i], target row neg[0][i]) and (pos[1][i], neg[1][i])
+ * for i < n_pos with weight w_dec, NI terms (ni[j], ni[j]) with weight w_ni.  Terms are grouped by z row, one segment per
+ * batch row (seg_ptr [n_b + 1]; call gd_rowpair_mse_f32 with seg_row = 0 .. n_b-1, n_seg = n_b), ordered by target row
+ * inside a segment, ties by term order: the gradient of a repeated endpoint is summed in a fixed order.
+ * pos / neg: int64 [2, ld] (row 1 at + ld).  term_o / term_w / term_kind [2 n_pos + n_ni].
+ * workspace >= gd_batch_loss_terms_workspace(n_b, 2 n_pos + n_ni) bytes, 256-byte aligned. */
+int64_t gd_batch_loss_terms_workspace(int32_t n_b, int64_t n_terms);
+int gd_batch_loss_terms(const int64_t* pos, int64_t ld_pos, const int64_t* neg, int64_t ld_neg, int32_t n_pos,
+                        const int32_t* ni, int32_t n_ni, int32_t n_b, float w_dec, float w_ni, int32_t* seg_ptr,
+                        int32_t* term_o, float* term_w, int32_t* term_kind, void* workspace, int64_t workspace_bytes,
+                        void* stream);
 
 /* ---------------------------------------------------------------- collectives (RCCL) ---- */
 
