@@ -449,11 +449,13 @@ def _layerwise_step(optimizer, alpha, r1, r2, l1, l2):
     return loss1 + loss2
 
 
-def nodeemb_minibatch(model, data, node_sets, negs, epochs, alpha, lr):
+def nodeemb_minibatch(model, data, node_sets, negs, epochs, alpha, lr, perm=None):
     """GNNDeleteNodeembTrainer.train_minibatch (gnndelete_nodeemb.py:352-443) without validation: per batch the
     original embeddings on ALL batch edges (Df included, :399-400), Del forward on the batch's S_Df edges with the
     batch's node masks, plain MSE (:357), negatives per batch (``negs``, consumed in order), layer-wise update.
-    -> per-step dicts(train_loss, train_loss_l, train_loss_r)."""
+    perm = a seed: every batch's edge columns (and their masks) are permuted before message passing - another
+    summation order in every scatter (a member of an fp32 ensemble); the Df edges the loss pairs with the negatives
+    keep the batch's order.  -> per-step dicts(train_loss, train_loss_l, train_loss_r)."""
     d = dict(data)
     d['sdf_node_1hop_mask_non_df_mask'], d['sdf_node_2hop_mask_non_df_mask'] = non_df_masks(
         d['x'].shape[0], d['directed_df_edge_index'], d['sdf_node_1hop_mask'], d['sdf_node_2hop_mask'])
@@ -461,16 +463,20 @@ def nodeemb_minibatch(model, data, node_sets, negs, epochs, alpha, lr):
     opt = make_optimizer(model, 'both_layerwise', lr)
     fct = nn.MSELoss()
     negs = iter(negs)
+    gp = torch.Generator().manual_seed(perm) if perm is not None else None
     logs = []
     for _ in range(epochs):
         model.train()
         for nodes in node_sets:
             b = pyg.saint_subgraph(d, nodes)
-            with torch.no_grad():
-                z1o, z2o = model.get_original_embeddings(b['x'], b['edge_index'], return_all_emb=True)
-            z1, z2 = model(b['x'], b['edge_index'][:, b['sdf_mask']], None, b['sdf_node_1hop_mask'], b['sdf_node_2hop_mask'],
-                           return_all_emb=True)
             pos = b['edge_index'][:, b['df_mask']]
+            ei, sdf = b['edge_index'], b['sdf_mask']
+            if gp is not None:
+                p = torch.randperm(ei.shape[1], generator=gp)
+                ei, sdf = ei[:, p], sdf[p]
+            with torch.no_grad():
+                z1o, z2o = model.get_original_embeddings(b['x'], ei, return_all_emb=True)
+            z1, z2 = model(b['x'], ei[:, sdf], None, b['sdf_node_1hop_mask'], b['sdf_node_2hop_mask'], return_all_emb=True)
             neg = next(negs)
             assert neg.shape[1] == pos.shape[1]
             r1, r2, l1, l2 = nodeemb_terms(z1, z2, z1o, z2o, pos, neg, b['sdf_node_1hop_mask_non_df_mask'],

@@ -147,3 +147,19 @@ def oracle_runner(gnn, data, state, neg, ni1, ni2, dtype, device, loss_type='bot
         return (ref.deletion1.deletion_weight.detach().double().cpu(), ref.deletion2.deletion_weight.detach().double().cpu(),
                 z1[m1.to(device)].double().cpu(), z2[m2.to(device)].double().cpu(), z2.detach())
     return step, snapshot, (z1o, z2o)
+
+
+def assert_del_weights_within_fp32_spread(tag, hip_w, w64, ens, iters):
+    """The Del WEIGHTS are a looser observable than the embeddings north_star bounds: Adam's first updates are
+    lr * m / sqrt(v) ~ +-lr per entry whatever the gradient's size, so the fp32 summation-order noise of a 180k-row
+    weight-gradient reduction shows up undamped in the weight, while the embeddings see it scaled by lr.  So they are held
+    to what fp32 arithmetic itself can deliver: HIP's distance to the fp64 oracle's weights <= 2 x the largest distance of
+    an fp32 ENSEMBLE (the same oracle in fp32 with several scatter orders; for the CPU-sized cases also the CPU oracle) to them
+    (+ 5e-5: the ensemble's own spread from run to run is a factor of four at this horizon - 3.5e-6 ... 1.4e-5 for W_D1 of
+    GCN at collab size - while HIP sits at 1.5e-5 every time; 5e-5 is 20 x below the 1e-3 this assertion replaced)."""
+    for k, name in enumerate(('W_D1', 'W_D2')):
+        d_ens = [rel_l2(e[k], w64[k]) for e in ens]
+        d_hip = rel_l2(hip_w[k], w64[k])
+        print(f'[{tag}] {name} after {iters} iterations, rel-L2 to the fp64 oracle: fp32 ensemble '
+              + ' '.join(f'{v:.2e}' for v in d_ens) + f' / HIP {d_hip:.2e}')
+        assert d_hip <= max(2.0 * max(d_ens), 5e-5), (name, d_hip, d_ens)

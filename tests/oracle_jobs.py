@@ -33,6 +33,9 @@ JOBS = {
     'full-collab-sage': ('linkpred', dict(workload='synth-collab', gnn='sage', df='in', df_size=5.0, iters=10)),
     'full-collab-gat': ('linkpred', dict(workload='synth-collab', gnn='gat', df='in', df_size=5.0, iters=10)),
     'full-nodecls-gat': ('nodecls', dict(epochs=10, lr=1e-2, alpha=0.5)),
+    # steps = tests/test_minibatch_full_size_gpu.py NUM_STEPS: one epoch of GraphSAINT batches, fp64 + the fp32 ensemble
+    'minibatch-collab-gcn': ('minibatch', dict(gnn='gcn', num_steps=16)),
+    'minibatch-collab-gat': ('minibatch', dict(gnn='gat', num_steps=16)),
     # (CPU-suite check of this machinery itself, never prefetched: tests/test_host_utils.py)
     'selftest-small': ('linkpred', dict(workload='synth-small', gnn='gcn', df='in', df_size=5.0, iters=2)),
 }
@@ -89,6 +92,81 @@ def nodecls_request():
     state = {k: v.clone() for k, v in hip.state_dict().items()}
     neg = negative_sampling(E, n, int(df_mask.sum()), generator=torch.Generator().manual_seed(4))
     return data, hip, state, neg
+
+
+MB_ALPHA, MB_LR = 0.5, 1e-3
+MB_PERMS = (None, 1, 2)        # edge orders inside each batch of the fp32 ensemble members
+
+
+def minibatch_request(gnn, num_steps, seed=42):
+    """The fused batch step's request at the size it is measured at (tools/experiments/minibatch_fused.py::setup):
+    synth-collab, 5 % IN deletion, a 128 -> 128 -> 64 model with seeded backbone and Del weights; `num_steps` GraphSAINT
+    node sets (8,192 roots, walk length 2) from the CPU sampler with a seeded generator, plus a batch without a Df edge and
+    one without an S1 row; per batch, as many seeded negative pairs as it has Df edges (pyg_semantics.saint_subgraph).
+    Everything is CPU-only and a pure function of the seeds.  -> (data, state, sets, negs, edge_sets, edge_negs)."""
+    from types import SimpleNamespace
+    sys.path.insert(0, ROOT)
+    from gnndelete_amd.framework import models as M
+    from gnndelete_amd.framework.data import prepare_edge_deletion, resolve_df_size
+    from gnndelete_amd.framework.synth import make_linkpred_dataset
+    from gnndelete_amd.framework.trainer.gnndelete_nodeemb import _non_df_masks
+    from gnndelete_amd.framework.trainer.sampler import RandomWalkSubgraphSampler
+    from oracle import pyg_semantics as pyg
+    torch.manual_seed(seed)
+    data, df = make_linkpred_dataset('synth-collab', seed=seed)
+    prepare_edge_deletion(data, df['in'], resolve_df_size(5.0, data.train_pos_edge_index.shape[1]))
+    _non_df_masks(data)
+    data.edge_index = data.train_pos_edge_index
+    n = data.num_nodes
+    torch.manual_seed(seed + 1)
+    cls = {'gcn': M.GCNDelete, 'gat': M.GATDelete, 'sage': M.SAGEDelete}[gnn]
+    model = cls(SimpleNamespace(in_dim=data.x.shape[1], hidden_dim=128, out_dim=64), data.sdf_node_1hop_mask,
+                data.sdf_node_2hop_mask)
+    gw = torch.Generator().manual_seed(seed + 2)
+    with torch.no_grad():
+        for p in (model.deletion1.deletion_weight, model.deletion2.deletion_weight):
+            p.copy_(torch.eye(p.shape[0]) * 0.5 + torch.randn(p.shape, generator=gw) * 0.05)
+    state = {k: v.clone() for k, v in model.state_dict().items()}
+    sampler = RandomWalkSubgraphSampler(data, batch_size=8192, walk_length=2, num_steps=num_steps,
+                                        generator=torch.Generator().manual_seed(seed + 3))
+    sets = list(sampler.node_sets())
+    E = data.train_pos_edge_index
+    df_nodes = torch.zeros(n, dtype=torch.bool)
+    df_nodes[E[:, data.df_mask].flatten()] = True
+    edge_sets = [sets[0][~df_nodes[sets[0]]], sets[1][~data.sdf_node_1hop_mask[sets[1]]]]   # no Df edge / no S1 row
+    small = {'edge_index': E, 'num_nodes': n, 'df_mask': data.df_mask}
+    gn = torch.Generator().manual_seed(seed + 4)
+
+    def negs_for(node_sets):
+        out = []
+        for nodes in node_sets:
+            m_df = int(pyg.saint_subgraph(small, nodes)['df_mask'].sum())
+            out.append(torch.randint(0, nodes.numel(), (2, m_df), generator=gn))
+        return out
+    negs = negs_for(sets)
+    return data, state, sets, negs, edge_sets, negs_for(edge_sets)
+
+
+def minibatch_checksum(state, sets, negs):
+    return checksum(state, torch.cat([torch.cat([s.double() for s in sets]), torch.cat([n_.flatten().double() for n_ in negs])]))
+
+
+def _run_minibatch(gnn, num_steps):
+    """One epoch of nodeemb_minibatch on the request's sampled batches: the fp64 oracle and the fp32 ensemble."""
+    from oracle import gnndelete_ref as R
+    data, state, sets, negs, _, _ = minibatch_request(gnn, num_steps)
+    torch.set_num_threads(min(THREADS, torch.get_num_threads()))
+    d = {k: v for k, v in data.items()}
+    runs = {}
+    for dtype, perm in [(torch.float64, None)] + [(torch.float32, p) for p in MB_PERMS]:
+        ref = R.TwoLayerDelete(gnn, data.x.shape[1], 128, 64, data.sdf_node_1hop_mask, data.sdf_node_2hop_mask)
+        ref.load_state_dict(state, strict=False)
+        ref = ref.to(dtype)
+        dd = dict(d, x=d['x'].to(dtype))
+        logs = R.nodeemb_minibatch(ref, dd, sets, negs, 1, MB_ALPHA, MB_LR, perm=perm)
+        runs[(str(dtype), perm)] = dict(logs=logs, w1=ref.deletion1.deletion_weight.detach().double().clone(),
+                                        w2=ref.deletion2.deletion_weight.detach().double().clone())
+    return dict(runs=runs, checksum=minibatch_checksum(state, sets, negs))
 
 
 def _run_linkpred(workload, gnn, df, df_size, iters):
@@ -189,7 +267,7 @@ def prefetch(names, members=()):
 
 def _run(name, out):
     kind, params = JOBS[name]
-    res = _run_linkpred(**params) if kind == 'linkpred' else _run_nodecls(**params)
+    res = {'linkpred': _run_linkpred, 'nodecls': _run_nodecls, 'minibatch': _run_minibatch}[kind](**params)
     torch.save(res, out + '.part')
     os.replace(out + '.part', out)
 

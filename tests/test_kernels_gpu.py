@@ -1652,3 +1652,113 @@ def test_del1_pass_forms_the_previous_input_gradient_itself(n_sel, rank1):
     check(lib.gd_del1_loss_wgrad_f32(ptr(p), p.stride(0), ptr(idx), n_sel, ptr(w), d, ptr(z_r), z_r.stride(0), ptr(bits_r), ptr(slot), ptr(tm),
                                      ptr(coef), ptr(cnt), None, 0, ptr(lp_r), ptr(ws_n0), nb, stream_ptr(p.device)), 'ref0')
     assert float((reduce_(ws_0) - reduce_(ws_n0)).norm() / reduce_(ws_n0).norm()) < 2e-6
+
+
+def _gat_hub_graph(seed):
+    """GAT test graph of the batch step's shapes: rows of in-degree 63, 64, 65, 1000 and 5000 (the appended self loop
+    counted: 1, 2 and 17 trips of the 64-edge loop, partial last groups), a source of out-degree 1000, explicit self
+    loops (dropped), multi-edges, and 50 isolated rows at the end (only their own loop)."""
+    g = torch.Generator().manual_seed(seed)
+    n, iso = 7000, 50
+    hubs = {10: 63, 11: 64, 12: 65, 13: 1000, 14: 5000}
+    parts = []
+    for hub, deg in hubs.items():
+        src = torch.randperm(n - iso - 100, generator=g)[:deg - 1] + 100
+        parts.append(torch.stack([src, torch.full_like(src, hub)]))
+    dst = torch.randperm(n - iso - 100, generator=g)[:1000] + 100
+    parts.append(torch.stack([torch.full_like(dst, 20), dst]))
+    rnd = torch.randint(100, n - iso, (2, 3 * n), generator=g)
+    parts += [rnd, rnd[:, :200], torch.arange(100, 140).repeat(2, 1)]
+    return torch.cat(parts, 1), n, hubs
+
+
+@pytest.mark.parametrize('d', [4, 8, 16, 20, 64, 128, 256, 260])
+def test_plain_gat_kernels_as_the_batch_step_calls_them_vs_fp64(d):
+    """gd_gat_aggregate_f32 / gd_gat_aggregate_bwd_f32 + ops.rank1_add2_, called as minibatch.MinibatchNodeembStep._agg /
+    _agg_bwd do (ops.gat_forward_raw reaches them only at widths that are not powers of two): y, the full input gradient
+    dh (message path + both score terms), da_src and da_dst against float64 autograd of pyg_semantics.gat_conv.  Every
+    lanes_per_row case (d/4 = 1 ... 64) and the VPL = 4 form (260), hub rows of several 64-edge trips, strided h / dy."""
+    import torch.nn.functional as F
+    from gnndelete_amd import _lib, ops
+    from gnndelete_amd._lib import check, ptr, stream_ptr
+    from gnndelete_amd.graph import build_csr
+    from oracle import pyg_semantics as pyg
+    ei, n, hubs = _gat_hub_graph(d)
+    slope = 0.2
+    g = torch.Generator().manual_seed(d + 1)
+    h64 = torch.randn(n, d, generator=g, dtype=torch.float64)
+    att_s, att_d = (torch.randn(d, generator=g, dtype=torch.float64) / d ** 0.5 for _ in range(2))
+    b = torch.randn(d, generator=g, dtype=torch.float64)
+    up = torch.randn(n, d, generator=g, dtype=torch.float64)
+    # fp64 references: gat_conv (weight = I) for y and dh; the same arithmetic with the scores exposed for da_src / da_dst
+    hr = h64.clone().requires_grad_(True)
+    want = pyg.gat_conv(hr, ei, torch.eye(d, dtype=torch.float64), att_s.view(1, 1, -1), att_d.view(1, 1, -1), b, slope)
+    want.backward(up)
+    hs = h64.clone().requires_grad_(True)
+    a_s, a_d = hs @ att_s, hs @ att_d
+    e2 = pyg.with_single_self_loops(ei, n)
+    alpha = pyg.segment_softmax(F.leaky_relu(a_s[e2[0]] + a_d[e2[1]], slope), e2[1], n)
+    y_s = pyg.scatter_rows(hs[e2[0]] * alpha[:, None], e2[1], n) + b
+    da_s_want, da_d_want = torch.autograd.grad(y_s, [a_s, a_d], up)
+    assert rel_l2(y_s.detach(), want.detach()) < 1e-12
+
+    dev = torch.device('cuda')
+    gr = build_csr(ei.to(dev), n, 'gat')
+    deg = (gr.rowptr[1:] - gr.rowptr[:-1]).cpu()
+    assert all(int(deg[r]) == k for r, k in hubs.items()) and int(deg[-1]) == 1
+    ld = d + 8                                             # row-strided h and dy, as gathered / sliced rows are
+    h = torch.zeros(n, ld, device=dev)[:, :d]
+    h.copy_(h64)
+    dy = torch.zeros(n, ld, device=dev)[:, :d]
+    dy.copy_(up)
+    att = (att_s.float().to(dev), att_d.float().to(dev))
+    sc = ops.row_dots(h, *att)
+    bias = b.float().to(dev)
+    L, st = _lib.lib(), stream_ptr(dev)
+    y = torch.empty(n, d, device=dev)
+    al = torch.empty(gr.nnz, device=dev)
+    check(L.gd_gat_aggregate_f32(ptr(gr.rowptr), ptr(gr.col), ptr(sc[0]), ptr(sc[1]), ptr(h), h.stride(0), ptr(y), y.stride(0),
+                                 ptr(bias), ptr(al), slope, n, d, st), 'gd_gat_aggregate_f32')
+    dh = torch.empty(n, d, device=dev)
+    da = torch.empty(2, n, device=dev)
+    de = torch.empty(gr.nnz, device=dev)
+    check(L.gd_gat_aggregate_bwd_f32(ptr(gr.rowptr), ptr(gr.col), ptr(al), ptr(gr.rowptr_t), ptr(gr.col_t), ptr(gr.perm_t),
+                                     ptr(sc[0]), ptr(sc[1]), ptr(h), h.stride(0), ptr(dy), dy.stride(0), ptr(dh), dh.stride(0),
+                                     ptr(da[0]), ptr(da[1]), ptr(de), slope, n, d, st), 'gd_gat_aggregate_bwd_f32')
+    ops.rank1_add2_(dh, da[0], att[0], da[1], att[1])
+    yc, dhc, dac = y.cpu().double(), dh.cpu().double(), da.cpu().double()
+    wy = want.detach()
+    err = (yc - wy).norm(dim=1) / wy.norm(dim=1)
+    for r in hubs:
+        assert float(err[r]) < TOL, (r, float(err[r]))
+    assert rel_l2(yc, wy) < TOL
+    assert rel_l2(dhc, hr.grad) < 5e-5
+    assert rel_l2(dhc[20], hr.grad[20]) < 5e-5                 # the out-degree-1000 source
+    assert rel_l2(dac[0], da_s_want) < 5e-5
+    assert rel_l2(dac[1], da_d_want) < 5e-5
+    for r in hubs:
+        assert abs(float(dac[1, r] - da_d_want[r])) <= 5e-5 * float(da_d_want.abs().max()), r
+
+
+@pytest.mark.parametrize('d', [4, 10, 64, 128])
+@pytest.mark.parametrize('n', [1, 63, 64, 65, 24_576])
+def test_row_dots_and_rank1_add2_vs_fp64(n, d):
+    """ops.row_dots (GAT's two attention scores) and ops.rank1_add2_ (their gradient's two rank-1 rows), both used by the
+    batch step, on row-strided views against float64; d = 10 takes each wrapper's fallback.  rank1_add2_ must leave the
+    padding columns of the strided rows alone."""
+    from gnndelete_amd import ops
+    g = torch.Generator().manual_seed(n * 7 + d)
+    ld = d + 4 if d % 4 == 0 else d + 2
+    base = torch.randn(n, ld, generator=g)
+    v1, v2 = torch.randn(d, generator=g), torch.randn(1, 1, d, generator=g)
+    hb = base.cuda()
+    h = hb[:, :d]
+    a1, a2 = ops.row_dots(h, v1.cuda(), v2.cuda())
+    x64 = base[:, :d].double()
+    assert rel_l2(a1.cpu(), x64 @ v1.double()) < TOL
+    assert rel_l2(a2.cpu(), x64 @ v2.double().reshape(-1)) < TOL
+    a, b_ = torch.randn(n, generator=g), torch.randn(n, generator=g)
+    ops.rank1_add2_(h, a.cuda(), v1.cuda(), b_.cuda(), v2.cuda())
+    want = x64 + a.double()[:, None] * v1.double()[None] + b_.double()[:, None] * v2.double().reshape(1, -1)
+    assert rel_l2(hb[:, :d].cpu(), want) < TOL
+    assert torch.equal(hb[:, d:].cpu(), base[:, d:])

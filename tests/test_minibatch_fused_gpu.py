@@ -42,6 +42,25 @@ def _node_sets(n, g):
             torch.tensor([17]), torch.tensor([3]), torch.arange(n)]
 
 
+def _assert_cut_matches_subgraph(cut, sampler, nodes):
+    """One cut of `nodes` against sampler.subgraph: edges, flags, counts, the four row lists and the Df edges, bit for bit."""
+    dev = cut.dev
+    cnt = cut.cut(nodes.to(dev))
+    ref = sampler.subgraph(nodes.to(dev))
+    got_ei, got_f = cut.batch_edges()
+    assert torch.equal(got_ei, ref.edge_index), nodes.numel()
+    assert torch.equal(got_f & 1, ref.sdf_mask.to(torch.uint8)) and torch.equal(got_f >> 1, ref.df_mask.to(torch.uint8))
+    assert cnt[:4] == [nodes.numel(), ref.edge_index.shape[1], int(ref.sdf_mask.sum()), int(ref.df_mask.sum())]
+    for k, key in enumerate(['sdf_node_1hop_mask', 'sdf_node_2hop_mask', 'sdf_node_1hop_mask_non_df_mask',
+                             'sdf_node_2hop_mask_non_df_mask']):
+        rows = ref[key].nonzero().flatten().to(torch.int32)
+        assert cnt[4 + k] == rows.numel() and torch.equal(cut.rows(k, rows.numel()), rows)
+    assert torch.equal(cut.df_index[:, :cnt[3]], ref.edge_index[:, ref.df_mask])
+    ei = ref.edge_index
+    assert cnt[8] == int((ei[0] != ei[1]).sum()) and cnt[9] == int((ei[0] != ei[1])[ref.sdf_mask].sum())
+    return ref
+
+
 def test_cut_is_bit_identical_to_subgraph():
     from gnndelete_amd.framework.trainer.sampler import RandomWalkSubgraphSampler
     from gnndelete_amd.minibatch import BatchCut
@@ -55,17 +74,7 @@ def test_cut_is_bit_identical_to_subgraph():
     lonely = torch.tensor([v for v in range(100, 3000) if int(((ei[0] == v) | (ei[1] == v)).sum()) == 0][:5] or [2999])
     sets.append(lonely.sort().values)
     for nodes in sets:
-        cnt = cut.cut(nodes.to(dev))
-        ref = sampler.subgraph(nodes.to(dev))
-        got_ei, got_f = cut.batch_edges()
-        assert torch.equal(got_ei, ref.edge_index), nodes.numel()
-        assert torch.equal(got_f & 1, ref.sdf_mask.to(torch.uint8)) and torch.equal(got_f >> 1, ref.df_mask.to(torch.uint8))
-        assert cnt[:4] == [nodes.numel(), ref.edge_index.shape[1], int(ref.sdf_mask.sum()), int(ref.df_mask.sum())]
-        for k, key in enumerate(['sdf_node_1hop_mask', 'sdf_node_2hop_mask', 'sdf_node_1hop_mask_non_df_mask',
-                                 'sdf_node_2hop_mask_non_df_mask']):
-            rows = ref[key].nonzero().flatten().to(torch.int32)
-            assert cnt[4 + k] == rows.numel() and torch.equal(cut.rows(k, rows.numel()), rows)
-        assert torch.equal(cut.df_index[:, :cnt[3]], ref.edge_index[:, ref.df_mask])
+        _assert_cut_matches_subgraph(cut, sampler, nodes)
     assert cut.e_cap >= d.edge_index.shape[1]
 
 
@@ -245,3 +254,216 @@ def test_cli_fused_minibatch_agrees_with_autograd_loop(tmp_path, monkeypatch):
             logs.append(json.load(f))
     assert logs[0]['minibatch_step'] == 'autograd' and logs[1]['minibatch_step'] == 'fused'
     assert abs(logs[0]['dt_auc'] - logs[1]['dt_auc']) < 2e-3
+
+
+# ------------------------------------------------------------------------------------------------ cut, CSR and loss-term shapes
+_CHUNK_ROWS = {0: 63, 1: 64, 2: 65, 3: 128, 4: 129}       # rows whose out-edges all land in the batch: 1 - 3 ballot chunks
+
+
+def _boundary_graph(n=3000, m=24000, seed=13):
+    """_synthetic's kind of graph, plus rows 0-4 whose ONLY out-edges are 63 / 64 / 65 / 128 / 129 edges to distinct
+    targets, and out-edges of node n - 1 (the last row of the sampler's rowptr) -> (data, {row: its targets})."""
+    from gnndelete_amd.framework.data import Data
+    g = torch.Generator().manual_seed(seed)
+    ei = torch.randint(0, n, (2, m), generator=g)
+    ei[0] = ei[0].clamp(min=len(_CHUNK_ROWS))
+    targets = {r: torch.randperm(n - 100, generator=g)[:k] + 100 for r, k in _CHUNK_ROWS.items()}
+    last = torch.stack([torch.full((40,), n - 1), torch.randint(0, n, (40,), generator=g)])
+    parts = [ei, last, ei[:, :50], torch.arange(20, 40).repeat(2, 1)]
+    parts += [torch.stack([torch.full_like(t_, r), t_]) for r, t_ in targets.items()]
+    ei = torch.cat(parts, 1)
+    e = ei.shape[1]
+    sdf = torch.rand(e, generator=g) < 0.6
+    df = sdf & (torch.rand(e, generator=g) < 0.1)
+    d = Data(num_nodes=n, edge_index=ei, x=torch.randn(n, 8, generator=g), sdf_mask=sdf, df_mask=df)
+    for k in ['sdf_node_1hop_mask', 'sdf_node_2hop_mask', 'sdf_node_1hop_mask_non_df_mask', 'sdf_node_2hop_mask_non_df_mask']:
+        d[k] = torch.rand(n, generator=g) < 0.4
+    return d, targets
+
+
+def _sized_set(n, size, g, must=()):
+    """A sorted node set of exactly `size` nodes holding `must` (node n - 1 included whenever it fits)."""
+    must = torch.as_tensor(sorted(set(must) | ({n - 1} if size > len(must) else set())), dtype=torch.long)[:size]
+    rest = torch.ones(n, dtype=torch.bool)
+    rest[must] = False
+    pool = rest.nonzero().flatten()
+    extra = pool[torch.randperm(pool.numel(), generator=g)[:size - must.numel()]]
+    return torch.cat([must, extra]).sort().values
+
+
+def test_cut_at_scan_and_ballot_chunk_boundaries():
+    """gd_induced_subgraph against sampler.subgraph, bit for bit, at the cut's shape boundaries: batch sizes around the
+    1024-row chunks of cut_scan_kernel (1, 1023, 1024, 1025, 2049, all nodes) and rows with exactly 63 / 64 / 65 / 128 /
+    129 in-batch out-edges (the 64-edge ballot chunks of cut_count_kernel / cut_write_kernel)."""
+    from gnndelete_amd.framework.trainer.sampler import RandomWalkSubgraphSampler
+    from gnndelete_amd.minibatch import BatchCut
+    d, targets = _boundary_graph()
+    n = d.num_nodes
+    dev = torch.device('cuda')
+    sampler = RandomWalkSubgraphSampler(d.clone().to(dev), batch_size=100)
+    cut = BatchCut(d, sampler, dev)
+    g = torch.Generator().manual_seed(3)
+    chunk_rows = set(_CHUNK_ROWS) | set(torch.cat(list(targets.values())).tolist())
+    sets = [torch.tensor([0]), torch.tensor([n - 1])]
+    sets += [_sized_set(n, k, g, chunk_rows if k > len(chunk_rows) else ()) for k in (1023, 1024, 1025, 2049)]
+    sets += [torch.arange(n), torch.tensor(sorted(chunk_rows))]
+    for nodes in sets:
+        ref = _assert_cut_matches_subgraph(cut, sampler, nodes)
+        if set(_CHUNK_ROWS) <= set(nodes.tolist()):
+            out_deg = torch.bincount(ref.edge_index[0].cpu(), minlength=nodes.numel())
+            assert [int(out_deg[r]) for r in _CHUNK_ROWS] == list(_CHUNK_ROWS.values())   # rows 0-4 are batch rows 0-4
+
+
+def test_cut_generation_stamps_buffer_growth_and_bad_ids():
+    """50 overlapping batches on one BatchCut (nodes of batch k that are not in batch k + 1 must leave no edge behind: the
+    relabel array is never cleared, only re-stamped), an edge-buffer grow-and-recut halfway through, and an out-of-range
+    node id (IndexError from the count vector) after which the same cut still cuts correctly."""
+    from gnndelete_amd.framework.trainer.sampler import RandomWalkSubgraphSampler
+    from gnndelete_amd.minibatch import BatchCut
+    d, _ = _boundary_graph(seed=17)
+    n = d.num_nodes
+    dev = torch.device('cuda')
+    sampler = RandomWalkSubgraphSampler(d.clone().to(dev), batch_size=100)
+    cut = BatchCut(d, sampler, dev, max_nodes=64)
+    g = torch.Generator().manual_seed(5)
+    grown = 0
+    for k in range(50):
+        width, start = (400, 37 * k) if k < 25 else (2000, 20 * k)     # small batches first, then ~4 x the edge buffer
+        window = (torch.arange(width) + start) % n
+        nodes = window[torch.rand(width, generator=g) < 0.75].unique()
+        if k % 7 == 3:
+            nodes = torch.cat([nodes, torch.tensor([n - 1])]).unique()
+        e_cap, reads = cut.e_cap, cut.reads
+        ref = _assert_cut_matches_subgraph(cut, sampler, nodes)
+        if ref.edge_index.shape[1] > e_cap:
+            assert cut.reads == reads + 2 and cut.e_cap >= ref.edge_index.shape[1], k     # grown, cut again
+            grown += 1
+        else:
+            assert cut.reads == reads + 1, k
+    assert grown >= 1 and cut.e_cap > 1024
+    for bad in (torch.tensor([0, 5, n]), torch.tensor([-1, 2, 9])):
+        with pytest.raises(IndexError):
+            cut.cut(bad.to(dev))
+        _assert_cut_matches_subgraph(cut, sampler, _sized_set(n, 1500, g))
+
+
+def _batch_csr_call(ei, n, gat):
+    """gd_batch_csr on edge list `ei` [2, e] (self loops already dropped, as the cut hands them over)."""
+    from gnndelete_amd import _lib
+    from gnndelete_amd._lib import check, ptr, stream_ptr
+    dev = torch.device('cuda')
+    e = ei.shape[1]
+    src, dst = torch.empty(e + n, dtype=torch.int64, device=dev), torch.empty(e + n, dtype=torch.int64, device=dev)
+    src[:e], dst[:e] = ei[0].to(dev), ei[1].to(dev)
+    L = _lib.lib()
+    nnz = e + n
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = {k: torch.empty(n + 1, **i32) for k in ('rowptr', 'rowptr_t')}
+    out.update({k: torch.empty(nnz, **i32) for k in ('col', 'col_t', 'perm_t')})
+    out['val'] = out['val_t'] = None
+    if not gat:
+        out['val'], out['val_t'] = torch.empty(nnz, device=dev), torch.empty(nnz, device=dev)
+    ws = torch.empty(max(256, L.gd_batch_csr_workspace(n, e)), dtype=torch.uint8, device=dev)
+    check(L.gd_batch_csr(ptr(src), ptr(dst), e, n, 1 if gat else 0, ptr(out['rowptr']), ptr(out['col']), ptr(out['val']),
+                         ptr(out['rowptr_t']), ptr(out['col_t']), ptr(out['perm_t']), ptr(out['val_t']), ptr(ws), ws.numel(),
+                         stream_ptr(dev)), 'gd_batch_csr')
+    return {k: (v.cpu() if v is not None else None) for k, v in out.items()}
+
+
+@pytest.mark.parametrize('case', ['no-edges', 'only-self-loops', 'duplicates', 'batch-24k'])
+def test_batch_csr_vs_numpy_and_fp64_norm(case):
+    """gd_batch_csr against an independent reference: pyg_semantics.with_single_self_loops, a stable numpy argsort per
+    direction and pyg_semantics.gcn_norm in float64 (no gd_csr_from_coo / gd_gcn_norm_f32 on the expected side).  Index
+    arrays exact; the GCN values within a few fp32 ulps (1 / sqrtf(deg) per endpoint)."""
+    from oracle import pyg_semantics as pyg
+    g = torch.Generator().manual_seed(len(case))
+    if case == 'no-edges':
+        n, raw = 7, torch.zeros(2, 0, dtype=torch.long)
+    elif case == 'only-self-loops':
+        n = 40
+        raw = torch.arange(0, n, 3).repeat(2, 1)
+    elif case == 'duplicates':
+        n = 300
+        raw = torch.randint(0, n, (2, 2000), generator=g)
+        raw = torch.cat([raw, raw[:, :500], raw[:, :100], torch.arange(0, n, 5).repeat(2, 1)], 1)
+        raw = raw[:, torch.randperm(raw.shape[1], generator=g)]
+    else:
+        n = 24_576
+        raw = torch.randint(0, n, (2, 240_000), generator=g)
+        raw = torch.cat([raw, raw[:, :1000], torch.stack([torch.randint(0, n, (3000,), generator=g), torch.full((3000,), 5)])], 1)
+    loops = raw[0] == raw[1]
+    e2 = pyg.with_single_self_loops(raw, n).numpy()
+    src, dst = e2[0], e2[1]
+    order = np.argsort(dst * n + src, kind='stable')
+    order_t = np.argsort(src * n + dst, kind='stable')
+    inv = np.empty_like(order)
+    inv[order] = np.arange(order.size)
+    want = dict(rowptr=np.concatenate([[0], np.cumsum(np.bincount(dst, minlength=n))]), col=src[order],
+                rowptr_t=np.concatenate([[0], np.cumsum(np.bincount(src, minlength=n))]), col_t=dst[order_t],
+                perm_t=inv[order_t])
+    _, w = pyg.gcn_norm(raw, n, torch.float64)
+    w = w.numpy()
+    for gat in (True, False):
+        got = _batch_csr_call(raw[:, ~loops], n, gat)
+        for key, val in want.items():
+            assert np.array_equal(got[key].numpy().astype(np.int64), val), (case, key, gat)
+        if gat:
+            continue
+        np.testing.assert_allclose(got['val'].numpy(), w[order], rtol=1e-6, atol=0, err_msg=case)
+        np.testing.assert_allclose(got['val_t'].numpy(), w[order_t], rtol=1e-6, atol=0, err_msg=case)
+
+
+def _loss_terms_call(pos, n_pos, neg, ni, n_b, w_dec, w_ni):
+    from gnndelete_amd import _lib
+    from gnndelete_amd._lib import check, ptr, stream_ptr
+    dev = torch.device('cuda')
+    L = _lib.lib()
+    n_terms = 2 * n_pos + ni.numel()
+    pos, neg, ni = pos.to(dev).contiguous(), neg.to(dev).contiguous(), ni.to(dev, torch.int32).contiguous()
+    seg_ptr = torch.full((n_b + 1,), -7, dtype=torch.int32, device=dev)
+    term_o = torch.empty(max(n_terms, 1), dtype=torch.int32, device=dev)
+    term_w = torch.empty(max(n_terms, 1), dtype=torch.float32, device=dev)
+    term_kind = torch.empty(max(n_terms, 1), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(256, L.gd_batch_loss_terms_workspace(n_b, n_terms)), dtype=torch.uint8, device=dev)
+    check(L.gd_batch_loss_terms(ptr(pos), pos.stride(0), ptr(neg), neg.stride(0), n_pos, ptr(ni), int(ni.numel()), n_b, w_dec,
+                                w_ni, ptr(seg_ptr), ptr(term_o), ptr(term_w), ptr(term_kind), ptr(ws), ws.numel(),
+                                stream_ptr(dev)), 'gd_batch_loss_terms')
+    return seg_ptr.cpu().numpy(), term_o[:n_terms].cpu().numpy(), term_w[:n_terms].cpu().numpy(), term_kind[:n_terms].cpu().numpy()
+
+
+@pytest.mark.parametrize('n_b,n_pos,n_ni,ld_pos,hub', [(500, 300, 200, 1024, False), (500, 0, 150, 0, False),
+                                                      (500, 120, 0, 4096, False), (64, 0, 0, 0, False),
+                                                      (2000, 700, 400, 700, True), (1, 3, 1, 5, False)])
+def test_batch_loss_terms_vs_numpy(n_b, n_pos, n_ni, ld_pos, hub):
+    """gd_batch_loss_terms against numpy: the terms (pos0 -> neg0, pos1 -> neg1, then NI rows onto themselves) grouped by
+    the z row they touch - what gd_csr_from_coo(targets, rows) yields: a stable sort on (row, target), so a row's terms
+    run by target and, for equal targets, in term order.  That order is the summation order of gd_rowpair_mse_f32.
+    seg_ptr, term_o and term_kind exact, term_w the DEC / NI weight of each term.  Cases: no DEC terms, no NI terms, none
+    at all, pos with a leading dimension above n_pos (the step passes df_index with stride e_cap), one row hit by 1,000
+    terms with repeated targets, terms on row n_b - 1."""
+    g = torch.Generator().manual_seed(n_b + n_pos)
+    pos = torch.zeros(2, max(ld_pos, n_pos, 1), dtype=torch.long)
+    pos[:, :n_pos] = torch.randint(0, n_b, (2, n_pos), generator=g)
+    neg = torch.randint(0, n_b, (2, n_pos), generator=g)
+    if hub:                                      # 1,000 terms on row 7, targets from a small range: equal (row, target) pairs
+        pos[0, :500] = 7
+        pos[1, :500] = 7
+        neg[:, :500] = torch.randint(0, 9, (2, 500), generator=g)
+    if n_pos:
+        pos[0, n_pos - 1] = n_b - 1
+    ni = torch.randperm(n_b, generator=g)[:n_ni].sort().values
+    if n_ni:
+        ni[-1] = n_b - 1
+        ni = ni.unique()
+    w_dec, w_ni = 0.25 / max(n_pos, 1), 0.125 / max(ni.numel(), 1)
+    seg_ptr, term_o, term_w, term_kind = _loss_terms_call(pos, n_pos, neg, ni, n_b, w_dec, w_ni)
+    rows = np.concatenate([pos[0, :n_pos].numpy(), pos[1, :n_pos].numpy(), ni.numpy()])
+    tgts = np.concatenate([neg[0].numpy(), neg[1].numpy(), ni.numpy()])
+    kind = np.concatenate([np.zeros(2 * n_pos, np.int64), np.ones(ni.numel(), np.int64)])
+    order = np.argsort(rows.astype(np.int64) * n_b + tgts, kind='stable')
+    assert np.array_equal(seg_ptr, np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n_b))]))
+    assert np.array_equal(term_o, tgts[order])
+    assert np.array_equal(term_kind, kind[order])
+    assert np.array_equal(term_w, np.where(kind[order] == 1, np.float32(w_ni), np.float32(w_dec)).astype(np.float32))
+    if hub:
+        assert seg_ptr[8] - seg_ptr[7] >= 1000
