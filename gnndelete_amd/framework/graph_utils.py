@@ -92,3 +92,30 @@ def negative_sampling(edge_index, num_nodes=None, num_neg_samples=None, generato
         tries += 1
     got = got[:want]
     return torch.stack([got // n, got % n])
+
+
+def positive_edge_keys(edge_index, num_nodes=None):
+    """The sorted unique keys `src * n + dst` negative_sampling builds on every call: once per request."""
+    n = int(edge_index.max()) + 1 if num_nodes is None else int(num_nodes)
+    return torch.unique(edge_index[0] * n + edge_index[1])
+
+
+def negative_sampling_cached(pos_keys, num_nodes, num_neg_samples, generator=None):
+    """negative_sampling against the keys of positive_edge_keys(edge_index, num_nodes): the same randint calls, candidate
+    counts and order, hence the same tensor for the same generator state - without the per-call torch.unique over every
+    edge of the graph."""
+    n, want = int(num_nodes), int(num_neg_samples)
+    dev = pos_keys.device
+    got = torch.empty(0, dtype=torch.long, device=dev)
+    tries = 0
+    while got.numel() < want and tries < 64:
+        m = int((want - got.numel()) * 1.2) + 16
+        cand = torch.randint(0, n * n, (m,), generator=generator, device='cpu').to(dev)
+        ok = (cand // n != cand % n)
+        loc = torch.searchsorted(pos_keys, cand).clamp(max=max(pos_keys.numel() - 1, 0))
+        if pos_keys.numel():
+            ok &= pos_keys[loc] != cand
+        got = torch.cat([got, cand[ok]])
+        tries += 1
+    got = got[:want]
+    return torch.stack([got // n, got % n])

@@ -148,31 +148,64 @@ class GNNDeleteTrainer(Trainer):
             nodes32 = nodes.to(torch.int32).contiguous()
         del pair_mask
         neg_size = int(data.df_mask.sum())
+        engine = draw = None
+        if getattr(args, 'fused_edgeprob', False):
+            # --fused_edgeprob: the same step on the fused HIP engine (gnndelete_amd/edgeprob.py), where it applies
+            from ...edgeprob import EdgeprobEngine, fused_edgeprob_unsupported
+            from .. import graph_utils
+            from .gnndelete_nodeemb import _adam_hyper
+            reason = fused_edgeprob_unsupported(model, args, optimizer)
+            if reason is None and neg_size < 1:
+                reason = 'no Df edges'
+            if reason is None:
+                lr, betas, eps = _adam_hyper(optimizer)
+                engine = EdgeprobEngine(model, data.x, e_sdf, df_edges, nodes32 if target is not None else None, target, n_pairs,
+                                        lr, betas, eps, history=max(16, args.epochs))
+                engine.import_adam_state(optimizer)
+                self._edgeprob_engine = engine
+                if negative_sampling is graph_utils.negative_sampling:
+                    # same draws as negative_sampling, without its torch.unique over every edge on every epoch
+                    pos_keys = graph_utils.positive_edge_keys(edges, data.num_nodes)
+                    draw = lambda: graph_utils.negative_sampling_cached(pos_keys, data.num_nodes, neg_size)
+                else:                                           # (the module-level name is the tests' seam)
+                    draw = lambda: negative_sampling(edge_index=edges, num_nodes=data.num_nodes, num_neg_samples=neg_size)
+            else:
+                print(f'--fused_edgeprob: {reason}; running the autograd loop', flush=True)
+            self.trainer_log['edgeprob_step'] = 'fused' if engine is not None else 'autograd'
         best_metric = 0
         for epoch in range(args.epochs):
             model.train()
             start = time.time()
-            z = model(data.x, e_sdf)
-            neg = negative_sampling(edge_index=edges, num_nodes=data.num_nodes, num_neg_samples=neg_size)
-            df_logits = model.decode(z, df_edges, neg)
-            loss_r = F.mse_loss(df_logits[:neg_size], df_logits[neg_size:])
-            if target is not None:
-                loss_l = ops.pairs_sigmoid_mse(z, nodes32, target, n_pairs)
+            if engine is not None:
+                engine.step(draw())
             else:
-                loss_l = torch.tensor(0.0, device=device)
-            loss = 0.5 * loss_r + 0.5 * loss_l
-            loss.backward()
-            optimizer.step()
-            optimizer.zero_grad()
+                z = model(data.x, e_sdf)
+                neg = negative_sampling(edge_index=edges, num_nodes=data.num_nodes, num_neg_samples=neg_size)
+                df_logits = model.decode(z, df_edges, neg)
+                loss_r = F.mse_loss(df_logits[:neg_size], df_logits[neg_size:])
+                if target is not None:
+                    loss_l = ops.pairs_sigmoid_mse(z, nodes32, target, n_pairs)
+                else:
+                    loss_l = torch.tensor(0.0, device=device)
+                loss = 0.5 * loss_r + 0.5 * loss_l
+                loss.backward()
+                optimizer.step()
+                optimizer.zero_grad()
             if (epoch + 1) % self.args.valid_freq == 0:
+                if engine is not None:
+                    cur = dict(zip(('train_loss', 'train_loss_l', 'train_loss_r'), engine.last_losses()))   # the block's host read
+                    engine.export_adam_state(optimizer)         # (a checkpoint below carries the optimizer's state)
+                else:
+                    cur = {'train_loss': loss.item(), 'train_loss_l': loss_l.item(), 'train_loss_r': loss_r.item()}
                 valid_loss, dt_auc, dt_aup, df_auc, df_aup, df_logit, _, valid_log = self.eval(model, data, 'val')
                 valid_log['epoch'] = epoch
-                self._record({'epoch': epoch, 'train_loss': loss.item(), 'train_loss_l': loss_l.item(),
-                              'train_loss_r': loss_r.item(), 'train_time': time.time() - start}, valid_log)
+                self._record({'epoch': epoch, **cur, 'train_time': time.time() - start}, valid_log)
                 if dt_auc + df_auc > best_metric:
                     best_metric = dt_auc + df_auc
                     print(f'Save best checkpoint at epoch {epoch:04d}. Valid loss = {valid_loss:.4f}')
                     torch.save({'model_state': model.state_dict(), 'optimizer_state': optimizer.state_dict()},
                                os.path.join(args.checkpoint_dir, 'model_best.pt'))
+        if engine is not None:
+            engine.export_adam_state(optimizer)
         torch.save({'model_state': {k: v.to('cpu') for k, v in model.state_dict().items()},
                     'optimizer_state': optimizer.state_dict()}, os.path.join(args.checkpoint_dir, 'model_final.pt'))

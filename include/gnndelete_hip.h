@@ -43,7 +43,9 @@ extern "C" {
                                 gd_agg_gemm_f32 and gd_spmm_csr_rowgroup_f32 removed (opt-in forms nobody defaulted);
                              9: gd_rows_gemm_accumulate_f32; gd_rows_gemm_select_f32 / gd_rows_gemm_dots_f32 run weight-stationary with a selector
                                 AND an index list; the one-launch item kernels abort on a misaligned XCD range table instead of deadlocking;
-                                gd_induced_subgraph, gd_batch_csr, gd_batch_loss_terms (+ their _workspace queries): the GraphSAINT batch step */
+                                gd_induced_subgraph, gd_batch_csr, gd_batch_loss_terms (+ their _workspace queries): the GraphSAINT batch step;
+                                gd_edgeprob_dec_f32, gd_edge_incidence (+ their _workspace queries), gd_rows_add_f32, gd_edgeprob_record_f32:
+                                the fused edge-probability step (entries added, none changed: the version stays) */
 
 enum {
   GD_OK = 0,
@@ -655,6 +657,46 @@ int64_t gd_pairs_sigmoid_mse_workspace(int32_t n_s, int32_t d);
 int gd_pairs_sigmoid_mse_f32(const float* z, int64_t ld_z, const int32_t* nodes, int32_t n_s, int32_t d,
                              const float* target, int64_t ld_t, float inv_count,
                              float* loss, float* dz, float* workspace, void* stream);
+
+/* ---------------------------------------------------------------- fused edge-probability step (csrc/edgeprob.hip) ---- */
+
+/* DEC term of GNNDeleteTrainer.train_fullbatch (framework/trainer/gnndelete.py:221-233), value and logit gradients:
+ *     a_k = <z[pos[0][k]], z[pos[1][k]]>,  b_k = <z[neg[0][k]], z[neg[1][k]]>,  diff_k = a_k - b_k        (k < m)
+ *     loss[0] = (1/m) sum_k diff_k^2;   w[k] = coef * 2 * diff_k / m,  w[m + k] = -w[k]
+ * i.e. w is d(coef * loss)/d(logit) of the 2m decoded edges in the decoder's [pos | neg] order.  pos / neg: int64
+ * [2, m] with row pitches ld_pos / ld_neg (elements); an edge with an endpoint outside [0, n_nodes) counts as a zero dot
+ * product (nothing outside z is read).  With src_edge / inc_ptr / w_inc (all three or none; from gd_edge_incidence over
+ * the 2m edges [pos | neg] and n_nodes) the finishing launch also writes w_inc[k] = w[src_edge[k]] for every incidence
+ * k < inc_ptr[n_nodes] - the order gd_edge_dot_bwd_f32 reads.  loss is summed in a fixed order (one partial per block,
+ * added in block order by one thread; no float atomics): the same bits every call.  workspace:
+ * gd_edgeprob_dec_workspace(m, d) floats.  d % 4 == 0, 16-byte aligned rows of z (GD_E_DIM / GD_E_ALIGN otherwise);
+ * m == 0 is GD_E_DIM (upstream's MSE of nothing is NaN).  Two launches. */
+int64_t gd_edgeprob_dec_workspace(int64_t m, int32_t d);
+int gd_edgeprob_dec_f32(const float* z, int64_t ld_z, int64_t n_nodes, int32_t d, const int64_t* pos, int64_t ld_pos,
+                        const int64_t* neg, int64_t ld_neg, int64_t m, float coef, float* w, float* loss,
+                        const int32_t* src_edge, const int64_t* inc_ptr, float* w_inc, float* workspace, void* stream);
+
+/* Node-major incidence list of n_edges edges (e0[k], e1[k]) over n_nodes nodes, as gd_edge_dot_bwd_f32 walks it:
+ *     inc_ptr [n_nodes + 1] int64;  other [2 n_edges] int32 = the other endpoint;  src_edge [2 n_edges] int32 = the edge
+ * in exactly the order of a STABLE sort of cat(e0, e1) by node id (entry p < n_edges is endpoint e0[p] of edge p, entry
+ * p >= n_edges endpoint e1[p - n_edges] of edge p - n_edges) - what ops._EdgeDot.backward builds with torch.sort +
+ * searchsorted.  Integer arithmetic only (a histogram, one scan, a fill and a rank pass); the result does not depend on
+ * the order the integer atomics arrive in.  An edge with an endpoint outside [0, n_nodes) gets no entries (inc_ptr[n_nodes]
+ * < 2 n_edges then; the tail of other / src_edge is not written).  workspace: gd_edge_incidence_workspace() BYTES. */
+int64_t gd_edge_incidence_workspace(int64_t n_nodes, int64_t n_edges);
+int gd_edge_incidence(const int64_t* e0, const int64_t* e1, int64_t n_edges, int64_t n_nodes, int64_t* inc_ptr,
+                      int32_t* other, int32_t* src_edge, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* dz[nodes[i], :] += scale * src[i, :] for i < n_s: the compact [n_s, d] pair-term gradient of
+ * gd_pairs_sigmoid_mse_f32 joins a dense [n_rows, d] gradient.  nodes must be UNIQUE (plain vector loads and stores, no
+ * atomics); rows outside [0, n_rows) are skipped.  d % 4 == 0, 16-byte aligned rows. */
+int gd_rows_add_f32(float* dz, int64_t ld_dz, int64_t n_rows, const int32_t* nodes, int32_t n_s, const float* src,
+                    int64_t ld_src, float scale, int32_t d, void* stream);
+
+/* hist[*pos % capacity] = (coef_r * *loss_r + coef_l * *loss_l, *loss_l, *loss_r); ++*pos.  loss_l == NULL: 0.
+ * hist: [capacity, 3] floats.  One thread; graph-capturable. */
+int gd_edgeprob_record_f32(const float* loss_r, const float* loss_l, float coef_r, float coef_l, float* hist,
+                           int32_t capacity, int32_t* pos, void* stream);
 
 /* ---------------------------------------------------------------- optimizer ------------ */
 
