@@ -101,6 +101,9 @@ PROTOTYPES = {
     'gd_del1_chain_loss_wgrad_f32': (ctypes.c_int, [_p, _i64, _p, _i32, _p, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _i32, _p]),
     'gd_del1_loss_wgrad_f32': (ctypes.c_int, [_p, _i64, _p, _i32, _p, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _i32, _p]),
     'gd_rowtarget_mse_blocks': (_i32, [_i32]),
+    'gd_rowfold_loss_blocks': (_i32, [_i32]),
+    'gd_rowfold_loss_f32': (ctypes.c_int, [_i32, _p, _i64, _p, _i32, _i32, _p, _p, _p, _p, _i32, _p, _i64, _p, _p]),
+    'gd_rowfold_kld_scale_f32': (ctypes.c_int, [_p, _i32, _f32, _f32, _f32, _f32, _p, _p, _i32, _i32, _p, _i64, _p, _p]),
     'gd_loss_finalize_f32': (ctypes.c_int, [_p, _i32, _p, _i32, _p, _p, _i32, _p, _p, _p]),
     'gd_pairs_sigmoid_mse_workspace': (_i64, [_i32, _i32]),
     'gd_pairs_sigmoid_mse_f32': (ctypes.c_int, [_p, _i64, _p, _i32, _i32, _p, _i64, _f32, _p, _p, _p, _p]),

@@ -672,3 +672,227 @@ extern "C" int gd_rowpair_loss_f32(int32_t kind, const float* a, int64_t ld_a, c
     hipLaunchKernelGGL((rowpair_loss_kernel<1>), grid, block, 0, (hipStream_t)stream, a, ld_a, ia, b, ld_b, ib, n_rows, d, val, grad, ld_g);
   return launched("rowpair_loss");
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// The same two row losses in the PRE-FOLDED (row-target) form of gd_rowtarget_mse_f32, for runs whose targets never
+// change: all terms t of a touched row u (targets o_t, count c_u) are folded once, on the host in fp64, into one
+// row tm[u,:], and a step streams z[row_u], tm[u] and writes dz[row_u] once.
+//   family 0 (cosine):  tm = U = sum_t o_t / max(|o_t|, 1e-8)
+//        sum_t (1 - cos(z, o_t)) = c - <z, U> / max(|z|, 1e-8)                                  -> sums[kind_u]
+//        dz = coef_u (-U / |z| + <z, U> z / |z|^3)     (|z| under the clamp: coef_u (-U / 1e-8), the denominator is a constant)
+//   family 1 (KLD):     tm = T = sum_t softmax(o_t)
+//        sum_t KL(softmax(o_t) || softmax(z)) = K_u + c KL(T / c || softmax(z)),   K_u >= 0 a constant of the fold
+//        c KL(T / c || softmax(z)) = sum_j T_j (log T_j - log c - log_softmax(z)_j)           -> sums[kind_u]
+//        dz = coef_u (c softmax(z) - T)                 (still to be scaled by exp(-KL_kind / n) / n: pass B below)
+// Softmax, dots and norms run over the first d_valid columns; dz is written as zero behind them.  A wave takes 64
+// consecutive loss rows (one coalesced fetch of row, coef, cnt, kind), its G lane groups walk them, a float4 per lane;
+// the row reductions are cross-lane inside the group; per-block partials as in rowtarget_mse_kernel.
+namespace gd {
+
+template <int LPR>
+__device__ __forceinline__ float lanes_max(float v) {
+#pragma unroll
+  for (int off = 1; off < LPR; off <<= 1) v = fmaxf(v, __shfl_xor(v, off));
+  return v;
+}
+
+template <int LPR, int FAMILY>
+__global__ __launch_bounds__(256) void rowfold_loss_kernel(
+    const float* __restrict__ z, int64_t ld_z, const float* __restrict__ tm, int32_t d4, int32_t d_valid,
+    const int32_t* __restrict__ row_idx, const float* __restrict__ coef, const float* __restrict__ cnt,
+    const int32_t* __restrict__ kind, int32_t n_rows, float* __restrict__ dz, int64_t ld_dz,
+    float* __restrict__ partials) {
+  constexpr int G = kWave / LPR;
+  __shared__ float red[2][4];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int g = lane / LPR, li = lane % LPR;
+  const int u0 = (blockIdx.x * 4 + wave) * kWave;
+  float s0 = 0.f, s1 = 0.f;
+  if (u0 < n_rows) {                                        // (wave-uniform)
+    const int n_here = min(kWave, n_rows - u0);
+    const bool live = lane < n_here;
+    const int row_l = live ? row_idx[u0 + lane] : 0;
+    const float coef_l = live ? coef[u0 + lane] : 0.f;
+    // count with the kind folded into the sign: DEC (kind 0) > 0, NI (kind 1) stored negative
+    const float cnt_l = live ? (kind[u0 + lane] ? -cnt[u0 + lane] : cnt[u0 + lane]) : 0.f;
+    const int trips = (n_here + G - 1) / G;
+    for (int t = 0; t < trips; ++t) {                       // (every lane of the wave makes every trip: the cross-lane steps need them)
+      const int j = t * G + g;
+      const bool ok = j < n_here;
+      const int row = __shfl(row_l, j & 63);
+      const float cf = __shfl(coef_l, j & 63);
+      const float cn = __shfl(cnt_l, j & 63);
+      const float c = ok ? fabsf(cn) : 1.f;
+      const bool in = ok && li < d4;
+      const float4 zv = in ? reinterpret_cast<const float4*>(z + (int64_t)row * ld_z)[li] : f4_zero();
+      const float4 tv = in ? reinterpret_cast<const float4*>(tm + (int64_t)(u0 + j) * d4 * 4)[li] : f4_zero();
+      const float zz[4] = {zv.x, zv.y, zv.z, zv.w}, tt[4] = {tv.x, tv.y, tv.z, tv.w};
+      bool valid[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) valid[k] = in && li * 4 + k < d_valid;
+      float gr[4], val;
+      if (FAMILY == 0) {
+        float dot = 0.f, nn = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float zk = valid[k] ? zz[k] : 0.f;
+          dot = fmaf(zk, valid[k] ? tt[k] : 0.f, dot);
+          nn = fmaf(zk, zk, nn);
+        }
+        dot = lanes_sum<LPR>(dot);
+        nn = lanes_sum<LPR>(nn);
+        const float nz = sqrtf(nn);
+        const float den = fmaxf(nz, 1e-8f);                 // (the clamp of F.cosine_similarity, as in rowpair_loss_kernel)
+        const float cs = dot / den;
+        const float ca = nz < 1e-8f ? 0.f : cs / nn;
+        val = c - cs;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gr[k] = valid[k] ? cf * (ca * zz[k] - tt[k] / den) : 0.f;
+      } else {
+        float m = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) m = fmaxf(m, valid[k] ? zz[k] : -INFINITY);
+        m = lanes_max<LPR>(m);
+        if (!ok) m = 0.f;
+        float e[4], se = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { e[k] = valid[k] ? expf(zz[k] - m) : 0.f; se += e[k]; }
+        se = lanes_sum<LPR>(se);
+        if (!ok) se = 1.f;
+        const float lse = m + logf(se), logc = logf(c), c_se = c / se;
+        float kl = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const bool on = valid[k] && tt[k] > 0.f;             // (xlogy convention of F.kl_div: 0 where the target is 0)
+          // log(T_j / (c softmax(z)_j)) as the log of ONE ratio near 1 where exp(z_j - m) has not underflowed: a trained request has
+          // KL << cross entropy, and the difference of three logs of magnitude log d (every row in the same argument range, so
+          // the 1-ulp errors of logf do not average out) lost 1e-5 of it; the log-domain form takes the far tails
+          const float ce = c * e[k];
+          const float lr = ce > 1e-30f ? logf(tt[k] * se / ce) : logf(tt[k]) - logc - (zz[k] - lse);
+          kl += on ? tt[k] * lr : 0.f;
+          gr[k] = valid[k] ? cf * (c_se * e[k] - tt[k]) : 0.f;
+        }
+        val = lanes_sum<LPR>(kl);
+      }
+      if (ok && li == 0) { if (cn >= 0.f) s0 += val; else s1 += val; }
+      if (dz && in) reinterpret_cast<float4*>(dz + (int64_t)row * ld_dz)[li] = make_float4(gr[0], gr[1], gr[2], gr[3]);
+    }
+  }
+  s0 = wave_sum(s0);
+  s1 = wave_sum(s1);
+  if (lane == 0) { red[0][wave] = s0; red[1][wave] = s1; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partials[2 * blockIdx.x + 0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    partials[2 * blockIdx.x + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+  }
+}
+
+// Pass B of the bounded KLD, two launches.  First ONE block adds pass A's per-block partials up in a fixed order and stores
+//   scales[kind] = exp(-(sum_kind + k_kind) * inv_n_kind) * inv_n_kind          (= d (1 - exp(-KL / n)) / d KL)
+__global__ __launch_bounds__(256) void rowfold_kld_scalars_kernel(
+    const float* __restrict__ partials, int32_t n_part, float k0, float k1, float inv_n0, float inv_n1,
+    float* __restrict__ scales) {
+  __shared__ float red[2][256];
+  float a = 0.f, b = 0.f;
+  for (int i = threadIdx.x; i < n_part; i += 256) { a += partials[2 * i]; b += partials[2 * i + 1]; }
+  red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (threadIdx.x < off) { red[0][threadIdx.x] += red[0][threadIdx.x + off]; red[1][threadIdx.x] += red[1][threadIdx.x + off]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    scales[0] = expf(-(red[0][0] + k0) * inv_n0) * inv_n0;
+    scales[1] = expf(-(red[1][0] + k1) * inv_n1) * inv_n1;
+  }
+}
+
+// ... then every block multiplies the dz rows of its 4 * (64 / LPR) loss rows by the scale of their kind.
+template <int LPR>
+__global__ __launch_bounds__(256) void rowfold_kld_scale_kernel(
+    const float* __restrict__ scales, const int32_t* __restrict__ row_idx, const int32_t* __restrict__ kind, int32_t n_rows,
+    int32_t d4, float* __restrict__ dz, int64_t ld_dz) {
+  constexpr int G = kWave / LPR;
+  const int lane = threadIdx.x & 63;
+  const int g = lane / LPR, li = lane % LPR;
+  const int u = (blockIdx.x * 4 + (threadIdx.x >> 6)) * G + g;
+  if (u < n_rows && li < d4) {
+    const float sc = scales[kind[u] ? 1 : 0];
+    float4* p = reinterpret_cast<float4*>(dz + (int64_t)row_idx[u] * ld_dz) + li;
+    const float4 v = *p;
+    *p = make_float4(sc * v.x, sc * v.y, sc * v.z, sc * v.w);
+  }
+}
+
+}  // namespace gd
+
+extern "C" int32_t gd_rowfold_loss_blocks(int32_t n_rows) { return n_rows > 0 ? (n_rows + 255) / 256 : 0; }
+
+extern "C" int gd_rowfold_loss_f32(int32_t family, const float* z, int64_t ld_z, const float* tm, int32_t d, int32_t d_valid,
+                                   const int32_t* row_idx, const float* coef, const float* cnt, const int32_t* kind,
+                                   int32_t n_rows, float* dz, int64_t ld_dz, float* partials, void* stream) {
+  using namespace gd;
+  GD_REQUIRE(family == 0 || family == 1, GD_E_DIM, "gd_rowfold_loss_f32: family must be 0 (cosine) or 1 (KLD), got %d", family);
+  GD_REQUIRE(d >= 4 && d <= 128 && d % 4 == 0, GD_E_DIM, "gd_rowfold_loss_f32: d=%d must be a multiple of 4 in [4, 128]", d);
+  GD_REQUIRE(d_valid >= 1 && d_valid <= d, GD_E_DIM, "gd_rowfold_loss_f32: d_valid=%d must lie in [1, d=%d]", d_valid, d);
+  GD_REQUIRE(n_rows >= 0, GD_E_DIM, "gd_rowfold_loss_f32: n_rows < 0");
+  if (n_rows == 0) return GD_OK;
+  GD_REQUIRE(z && tm && row_idx && coef && cnt && kind && partials, GD_E_NULL, "gd_rowfold_loss_f32: null pointer");
+  GD_REQUIRE(ld_z >= d && ld_z % 4 == 0 && (!dz || (ld_dz >= d && ld_dz % 4 == 0)), GD_E_DIM,
+             "gd_rowfold_loss_f32: row strides must be multiples of 4, at least d=%d", d);
+  GD_REQUIRE(aligned16(z) && aligned16(tm) && aligned16(dz), GD_E_ALIGN, "gd_rowfold_loss_f32: unaligned matrix");      // (dz may be NULL)
+  hipStream_t s = (hipStream_t)stream;
+  const int d4 = d / 4;
+  const int nb = (n_rows + 255) / 256;
+#define GD_RF_CASE(LPR)                                                                                                   \
+  do {                                                                                                                    \
+    if (family == 0) hipLaunchKernelGGL((rowfold_loss_kernel<LPR, 0>), dim3(nb), dim3(256), 0, s, z, ld_z, tm, d4, d_valid, \
+                                        row_idx, coef, cnt, kind, n_rows, dz, ld_dz, partials);                          \
+    else hipLaunchKernelGGL((rowfold_loss_kernel<LPR, 1>), dim3(nb), dim3(256), 0, s, z, ld_z, tm, d4, d_valid, row_idx,  \
+                            coef, cnt, kind, n_rows, dz, ld_dz, partials);                                               \
+  } while (0)
+  switch (lanes_per_row(d4)) {
+    case 1: GD_RF_CASE(1); break;
+    case 2: GD_RF_CASE(2); break;
+    case 4: GD_RF_CASE(4); break;
+    case 8: GD_RF_CASE(8); break;
+    case 16: GD_RF_CASE(16); break;
+    default: GD_RF_CASE(32); break;
+  }
+#undef GD_RF_CASE
+  return launched("rowfold_loss");
+}
+
+extern "C" int gd_rowfold_kld_scale_f32(const float* partials, int32_t n_blocks, float k_dec, float k_ni, float inv_n_dec,
+                                        float inv_n_ni, const int32_t* row_idx, const int32_t* kind, int32_t n_rows, int32_t d,
+                                        float* dz, int64_t ld_dz, float* scales, void* stream) {
+  using namespace gd;
+  GD_REQUIRE(d >= 4 && d <= 128 && d % 4 == 0, GD_E_DIM, "gd_rowfold_kld_scale_f32: d=%d must be a multiple of 4 in [4, 128]", d);
+  GD_REQUIRE(n_rows >= 0 && n_blocks >= 0 && n_blocks == gd_rowfold_loss_blocks(n_rows), GD_E_DIM,
+             "gd_rowfold_kld_scale_f32: n_blocks=%d is not gd_rowfold_loss_blocks(n_rows=%d)", n_blocks, n_rows);
+  GD_REQUIRE((n_blocks == 0 || partials) && (n_rows == 0 || !dz || (row_idx && kind)), GD_E_NULL, "gd_rowfold_kld_scale_f32: null pointer");
+  GD_REQUIRE(!dz || (ld_dz >= d && ld_dz % 4 == 0), GD_E_DIM, "gd_rowfold_kld_scale_f32: ld_dz must be a multiple of 4, at least d=%d", d);
+  GD_REQUIRE(aligned16(dz), GD_E_ALIGN, "gd_rowfold_kld_scale_f32: unaligned matrix");
+  GD_REQUIRE(scales, GD_E_NULL, "gd_rowfold_kld_scale_f32: null pointer (scales)");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(rowfold_kld_scalars_kernel, dim3(1), dim3(256), 0, s, partials, n_blocks, k_dec, k_ni, inv_n_dec, inv_n_ni, scales);
+  if (!dz || n_rows == 0) return launched("rowfold_kld_scalars");
+  const int d4 = d / 4;
+  const int lpr = lanes_per_row(d4);
+  const int per_block = 4 * (kWave / lpr);
+  const int nb = (n_rows + per_block - 1) / per_block;
+#define GD_KS_CASE(LPR) \
+  hipLaunchKernelGGL((rowfold_kld_scale_kernel<LPR>), dim3(nb), dim3(256), 0, s, scales, row_idx, kind, n_rows, d4, dz, ld_dz)
+  switch (lpr) {
+    case 1: GD_KS_CASE(1); break;
+    case 2: GD_KS_CASE(2); break;
+    case 4: GD_KS_CASE(4); break;
+    case 8: GD_KS_CASE(8); break;
+    case 16: GD_KS_CASE(16); break;
+    default: GD_KS_CASE(32); break;
+  }
+#undef GD_KS_CASE
+  return launched("rowfold_kld_scale");
+}

@@ -51,7 +51,7 @@ from .nn import GATConv, GCNConv, GINConv, RGCNConv, SAGEConv
 class PartitionedNodeembEngine:
     def __init__(self, model, x, edge_index, z1_ori, z2_ori, pos_edge, neg_edge, ni_mask1, ni_mask2, rank, world,
                  loss_type='both_layerwise', alpha=0.5, lr=1e-3, reduction='mean', use_graph=True, history=4096,
-                 reorder=True, group=None, edge_type=None, overlap=None):
+                 reorder=True, group=None, edge_type=None, overlap=None, loss_fct=None):
         """edge_type (R-GCN, BASELINE config 4): relation type per column of edge_index; x is then the entity id vector
         (the frozen embedding table is replicated and looked up once).
         overlap: run the halo exchanges on a communication stream UNDER the interior-row aggregation and the partial weight
@@ -61,6 +61,13 @@ class PartitionedNodeembEngine:
         multi-GPU RCCL group the synchronous one is the default, and bench.py switches the overlap on only after its
         child-process probe has reproduced the synchronous result with it."""
         assert loss_type in LOSS_TYPES, loss_type
+        if loss_fct is not None and loss_fct not in ('mse_mean', 'mse_sum'):
+            # (the bounded KLD's gradient carries exp(-KL / n), a scalar over ALL ranks' rows: an all-reduce in mid-step)
+            raise NotImplementedError(f'PartitionedNodeembEngine runs the MSE losses only (loss_fct={loss_fct!r}): the folded KLD / cosine '
+                                      'row losses of NodeembEngine have no row-partitioned form - the KLD scalar would need an all-reduce '
+                                      'in mid-step')
+        if loss_fct is not None and loss_fct != 'mse_' + reduction:       # (the argument exists for the refusal above only)
+            raise ValueError(f'PartitionedNodeembEngine: loss_fct={loss_fct!r} contradicts reduction={reduction!r}')
         conv1, conv2 = model.conv1, model.conv2
         if not isinstance(conv2, (GCNConv, GINConv, SAGEConv, GATConv, RGCNConv)):
             raise NotImplementedError('PartitionedNodeembEngine supports GCN, GIN, GraphSAGE, GAT and R-GCN backbones')

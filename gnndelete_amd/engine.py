@@ -19,6 +19,10 @@ HIP kernels - no autograd tape - laid out once over static buffers and captured 
             both_all).
 
 Per-step loss sums are appended to a device-side history without a host sync.
+
+With loss_fct = kld_* / cosine_* (--fused_row_losses) the loss stage of each layer is the folded row-loss launch
+(gd_rowfold_loss_f32, for the bounded KLD followed by gd_rowfold_kld_scale_f32) between the Del row product and the
+weight-gradient launch; the forms that fuse the MSE loss into a neighbouring kernel are off, the rest of the step is the same.
 """
 import os
 
@@ -39,6 +43,52 @@ def _loss_coefficients(loss_type, alpha):
     return alpha, 1.0                      # only2_all / only1: loss_l + alpha * loss_r
 
 
+LOSS_FAMILIES = {'mse_mean': ('mse', 'mean'), 'mse_sum': ('mse', 'sum'), 'kld_mean': ('kld', 'mean'), 'kld_sum': ('kld', 'sum'),
+                 'cosine_mean': ('cosine', 'mean'), 'cosine_sum': ('cosine', 'sum')}
+_ROWFOLD_FAMILY = {'cosine': 0, 'kld': 1}          # the `family` argument of gd_rowfold_loss_f32
+
+
+def fold_row_terms(family, z_ori, rows, tgt, kind, d_valid=None):
+    """Fold the KLD / cosine terms (z row rows[t], target z_ori[tgt[t]], kind[t]) per touched row, in fp64 and in a fixed order
+    (terms sorted by row, original order inside a row, one sequential segment_reduce per row - no index_add_).  Returns
+    (uniq rows, tm [U, d] fp64, counts, kind per row, [K_DEC, K_NI]) with, per row u of c terms,
+      cosine   tm = sum_t o_t / max(|o_t|, 1e-8), K = 0:       sum_t (1 - cos(z, o_t)) = c - <z, tm> / max(|z|, 1e-8)
+      kld      tm = T = sum_t softmax(o_t) over the first d_valid columns (zeros behind them),
+               K_u = sum_t sum_j t_j log t_j - sum_j T_j log(T_j / c) >= 0:
+               sum_t KL(softmax(o_t) || softmax(z)) = K_u + sum_j T_j (log(T_j / c) - log_softmax(z)_j)
+    Pure torch on the tensors' device: no HIP library needed."""
+    assert family in ('kld', 'cosine'), family
+    d = z_ori.shape[1]
+    dv = d if d_valid is None else int(d_valid)
+    device = z_ori.device
+    uniq, inv, c = torch.unique(rows, return_inverse=True, return_counts=True)
+    kind_u = torch.zeros(uniq.numel(), dtype=torch.int32, device=device)
+    kind_u[inv] = kind.to(torch.int32)
+    if uniq.numel() == 0:
+        return uniq, torch.zeros(0, d, dtype=torch.float64, device=device), c, kind_u, [0.0, 0.0]
+    order = torch.argsort(inv, stable=True)
+    o64 = z_ori[tgt[order]][:, :dv].double()
+    if family == 'cosine':
+        u = o64 / o64.norm(dim=1, keepdim=True).clamp_(min=1e-8)
+        tm = torch.segment_reduce(u, 'sum', lengths=c, axis=0)
+        k_row = torch.zeros(uniq.numel(), dtype=torch.float64, device=device)
+    else:
+        t = torch.softmax(o64, 1)
+        tm = torch.segment_reduce(t, 'sum', lengths=c, axis=0)
+        ent = torch.segment_reduce(torch.special.xlogy(t, t).sum(1), 'sum', lengths=c, axis=0)
+        k_row = (ent - torch.special.xlogy(tm, tm / c[:, None].double()).sum(1)).clamp_(min=0.0)
+    if dv < d:
+        tm = torch.nn.functional.pad(tm, (0, d - dv))
+    return uniq, tm, c, kind_u, [float(k_row[kind_u == 0].sum()), float(k_row[kind_u == 1].sum())]
+
+
+def logged_loss(family, raw_sum, k_const, n):
+    """The value the reference logs for one loss term from the raw device sum of its kind (fp64 tensors / floats):
+    mse (s + K) / n;  cosine s / n (the kernel adds up 1 - cos itself, K = 0);  kld 1 - exp(-(s + K) / n)."""
+    v = (raw_sum + k_const) / n
+    return 1.0 - torch.exp(-v) if family == 'kld' else v
+
+
 class _LayerTerms:
     """DEC + NI terms of one layer, folded per touched row (targets are fixed for the run).
 
@@ -48,16 +98,23 @@ class _LayerTerms:
     (folded once in fp64).  If some row carries both kinds (never the case for the reference's
     masks, where NI rows exclude the Df endpoints) the general segmented kernel is used instead."""
 
-    def __init__(self, pos_edge, neg_edge, ni_mask, z_ori, coef_r, coef_l, reduction, row_range=None, d_norm=None):
+    def __init__(self, pos_edge, neg_edge, ni_mask, z_ori, coef_r, coef_l, reduction, row_range=None, d_norm=None, family='mse'):
         """row_range=(lo, hi): keep only the terms whose z row lies in [lo, hi) (1-D row
         partition); the mean normalisers stay the GLOBAL term counts.  d_norm: the width the 'mean' reduction divides
-        by when z_ori carries zero padding columns behind it (NodeembEngine's padded class dimension)."""
+        by when z_ori carries zero padding columns behind it (NodeembEngine's padded class dimension).
+        family: 'mse' (above), or 'kld' / 'cosine' - the bounded-KLD and cosine-distance row losses, folded per touched row by
+        fold_row_terms() for gd_rowfold_loss_f32; their 'mean' divides by the number of terms, and d_norm is the width the KLD
+        softmax runs over."""
         device = z_ori.device
+        self.family = family
+        self.d_valid = z_ori.shape[1] if d_norm is None else int(d_norm)
         d = z_ori.shape[1]
         dn = d if d_norm is None else int(d_norm)
         pos, neg = pos_edge.to(device).long(), neg_edge.to(device).long()
         ni_rows = ni_mask.to(device).nonzero().flatten()
         m = pos.shape[1]
+        if family != 'mse':
+            dn = 1                                  # (batchmean / .mean() over the rows)
         self.n_r = (2 * m * dn) if reduction == 'mean' else 1
         self.n_l = (ni_rows.numel() * dn) if reduction == 'mean' else 1
         self.count_r, self.count_l = 2 * m, int(ni_rows.numel())
@@ -72,7 +129,25 @@ class _LayerTerms:
             rows, tgt, kind = rows[mine], tgt[mine], kind[mine]
         self.k_const = [0.0, 0.0]
         self.folded = not mixed
-        if self.folded:
+        if family != 'mse':
+            if mixed:
+                raise ValueError(f'the folded {family} loss needs one kind of term per row: a Neighborhood-Influence row of this request is an '
+                                 'endpoint of a deleted edge (the autograd loop handles such a request)')
+            if row_range is not None:
+                raise ValueError(f'the folded {family} loss has no row-partitioned form (its scalar would need an all-reduce in mid-step)')
+            uniq, tm, c, kind_u, self.k_const = fold_row_terms(family, z_ori, rows, tgt, kind, self.d_valid)
+            self.n_rows = int(uniq.numel())
+            self.row_idx = uniq.to(torch.int32)
+            self.tm = tm.float().contiguous()
+            self.cnt = c.float()
+            self.kind = kind_u
+            if family == 'cosine':                  # the gradient is final: static scale coef_kind / n_kind
+                self.coef = torch.where(kind_u == 0, w_r, w_l).float()
+            else:                                   # pass B multiplies exp(-KL_kind / n_kind) / n_kind in
+                self.coef = torch.where(kind_u == 0, float(coef_r), float(coef_l)).float()
+            self.scales = torch.zeros(2, dtype=torch.float32, device=device)      # the two KLD scalars of pass B
+            ws = 2 * _lib.lib().gd_rowfold_loss_blocks(self.n_rows)
+        elif self.folded:
             uniq, inv, c = torch.unique(rows, return_inverse=True, return_counts=True)
             # per-row sums over the row's loss terms in a FIXED order (terms sorted by row, original order inside a row; one
             # sequential sum per row): index_add_ adds with atomics in arrival order, and the constants of the loss LOG below
@@ -114,6 +189,8 @@ class _LayerTerms:
 
     def n_partial_blocks(self):
         """Blocks of per-block loss partials the folded kernel writes (for gd_loss_finalize_f32)."""
+        if self.family != 'mse':
+            return _lib.lib().gd_rowfold_loss_blocks(self.n_rows)
         return _lib.lib().gd_rowtarget_mse_blocks(self.n_rows) if self.folded and self.n_rows else 0
 
     def order_inside_first(self, idx, n_sel):
@@ -158,7 +235,20 @@ class _LayerTerms:
     def launch(self, z, dz, sums):
         """sums = None (folded form only): leave the partials for gd_loss_finalize_f32."""
         d = z.shape[1]
-        if self.folded:
+        if self.family != 'mse':
+            # pass A: row gradients (final for cosine) + per-block partial sums; pass B (KLD): the scalar of each kind, formed on
+            # the device from those partials, multiplied into the rows
+            assert sums is None
+            lib, st = _lib.lib(), stream_ptr(z.device)
+            check(lib.gd_rowfold_loss_f32(_ROWFOLD_FAMILY[self.family], ptr(z), z.stride(0), ptr(self.tm), d, min(self.d_valid, d),
+                                          ptr(self.row_idx), ptr(self.coef), ptr(self.cnt), ptr(self.kind), self.n_rows, ptr(dz),
+                                          dz.stride(0), ptr(self.partials), st), 'gd_rowfold_loss_f32')
+            if self.family == 'kld':
+                inv_r, inv_l = (1.0 / self.n_r if self.count_r else 0.0), (1.0 / self.n_l if self.count_l else 0.0)
+                check(lib.gd_rowfold_kld_scale_f32(ptr(self.partials), self.n_partial_blocks(), self.k_const[0], self.k_const[1], inv_r,
+                                                   inv_l, ptr(self.row_idx), ptr(self.kind), self.n_rows, d, ptr(dz), dz.stride(0),
+                                                   ptr(self.scales), st), 'gd_rowfold_kld_scale_f32')
+        elif self.folded:
             check(_lib.lib().gd_rowtarget_mse_f32(ptr(z), z.stride(0), ptr(self.tm), d, ptr(self.row_idx),
                                                   ptr(self.coef), ptr(self.cnt), ptr(self.kind), self.n_rows, ptr(dz),
                                                   dz.stride(0), ptr(sums), ptr(self.partials), stream_ptr(z.device)),
@@ -267,17 +357,38 @@ def _padded_out_shadow(model, o_pad):
     return SimpleNamespace(conv1=model.conv1, conv2=s2.to(dev), deletion1=model.deletion1, deletion2=del2)
 
 
+def padded_class_width(h, o, rgcn=False):
+    """The layer-2 width NodeembEngine runs a model of hidden width h and output width o at: a class dimension below 32 is padded
+    to GD_PAD_OUT (32 | 64, default 64; 0 = off) where h = 128, every other width stays."""
+    pad_to = int(os.environ.get('GD_PAD_OUT', '64'))
+    return pad_to if (not rgcn and o < 32 and pad_to in (32, 64) and h == 128) else o
+
+
 class NodeembEngine:
     """One object per unlearning request (fixed graph, fixed Df, fixed negatives)."""
 
     def __init__(self, model, x, edge_index, z1_ori, z2_ori, pos_edge, neg_edge, ni_mask1, ni_mask2,
                  loss_type='both_layerwise', alpha=0.5, lr=1e-3, reduction='mean', mask_1hop=None, mask_2hop=None,
                  use_graph=True, history=4096, reorder=True, cache_layer1=False, affected_rows_only=False,
-                 edge_type=None):
-        """edge_type (R-GCN only): relation type per column of edge_index (reverse edges included, as
+                 edge_type=None, loss_fct=None):
+        """loss_fct: 'mse_mean' | 'mse_sum' (default: 'mse_' + reduction) - the fused forms below - or 'kld_mean' | 'kld_sum' |
+        'cosine_mean' | 'cosine_sum': the same step with the folded row-loss launches (gd_rowfold_loss_f32, for KLD followed by
+        gd_rowfold_kld_scale_f32) between the Del row products and the weight-gradient launches; the MSE-specific fused forms
+        (loss inside the weight-gradient fetch, fused / chained Del-1, fused Del-2) are off, everything else - tail launch, graph
+        capture, cache_layer1, affected_rows_only, the update rules of every loss_type - is unchanged.
+        edge_type (R-GCN only): relation type per column of edge_index (reverse edges included, as
         delete_gnn.py:158-171 builds them); x is then the entity id vector the embedding table is indexed with."""
         assert loss_type in LOSS_TYPES, loss_type
+        if loss_fct is None:
+            loss_fct = 'mse_' + reduction
+        if loss_fct not in LOSS_FAMILIES:
+            raise ValueError(f'NodeembEngine: no fused step for loss_fct={loss_fct!r} (one of {sorted(LOSS_FAMILIES)})')
+        self.loss_fct = loss_fct
+        self.family, reduction = LOSS_FAMILIES[loss_fct]
+        self._mse = self.family == 'mse'
         conv1, conv2 = model.conv1, model.conv2
+        if not self._mse and isinstance(conv2, RGCNConv):
+            raise NotImplementedError('NodeembEngine: the folded KLD / cosine losses are not wired into the R-GCN step')
         if not isinstance(conv2, (GCNConv, GINConv, GATConv, SAGEConv, RGCNConv)):
             raise NotImplementedError(f'NodeembEngine: unsupported conv {type(conv2).__name__}')
         if isinstance(conv2, RGCNConv):
@@ -305,9 +416,8 @@ class NodeembEngine:
         # W_D2's top-left block is copied back into the caller's parameter at the end of every iteration.
         self._o_true = int(model.deletion2.deletion_weight.shape[0])
         self._user_wd2 = None
-        pad_to = int(os.environ.get('GD_PAD_OUT', '64'))
-        if (not isinstance(conv2, RGCNConv) and self._o_true < 32 and pad_to in (32, 64)
-                and model.deletion1.deletion_weight.shape[0] == 128):
+        pad_to = padded_class_width(model.deletion1.deletion_weight.shape[0], self._o_true, isinstance(conv2, RGCNConv))
+        if pad_to != self._o_true:
             self._user_wd2 = model.deletion2.deletion_weight
             model = _padded_out_shadow(model, pad_to)
             conv2 = model.conv2
@@ -340,8 +450,9 @@ class NodeembEngine:
         self.s1, self.s2 = int(self.idx1.numel()), int(self.idx2.numel())
         self.z1_ori, self.z2_ori = ops._f32_rows(z1_ori), ops._f32_rows(z2_ori)
         coef_r, coef_l = _loss_coefficients(loss_type, alpha)
-        self.t1 = _LayerTerms(pos_edge, neg_edge, ni_mask1, self.z1_ori, coef_r, coef_l, reduction)
-        self.t2 = _LayerTerms(pos_edge, neg_edge, ni_mask2, self.z2_ori, coef_r, coef_l, reduction, d_norm=self._o_true)
+        self.t1 = _LayerTerms(pos_edge, neg_edge, ni_mask1, self.z1_ori, coef_r, coef_l, reduction, family=self.family)
+        self.t2 = _LayerTerms(pos_edge, neg_edge, ni_mask2, self.z2_ori, coef_r, coef_l, reduction, d_norm=self._o_true,
+                              family=self.family)
         self.uses_l1 = loss_type in ('both_all', 'both_layerwise', 'only1')
         self.uses_l2 = loss_type != 'only1'
         # does a gradient of loss-2 w.r.t. W_D1 (through conv2) ever reach an optimizer step?
@@ -362,7 +473,7 @@ class NodeembEngine:
         self._out1 = self._out2 = 0
         mixed_ok = (self.t1.folded and self.t2.folded and os.environ.get('GD_NO_SPLIT_LOSS') != '1' and os.environ.get('GD_NO_SPLIT') != '1')
         inside2 = _rows_inside(self.t2, self.idx2, self.s2)
-        if (not inside2 and mixed_ok and self.s2 > 0 and self.o in (32, 64) and self.t2.n_rows > 0
+        if (not inside2 and mixed_ok and self._mse and self.s2 > 0 and self.o in (32, 64) and self.t2.n_rows > 0
                 and os.environ.get('GD_NO_FUSED_L2') != '1'):
             self._out2 = self.t2.n_rows - self.t2.order_inside_first(self.idx2, self.s2)
             inside2 = True
@@ -370,7 +481,7 @@ class NodeembEngine:
         self.p2 = torch.empty(n, self.o, **f32) if self._split2 else self.z2
         self.xs2 = None if self._split2 else torch.empty(max(1, self.s2), self.o, **f32)
         # ... and with that, Del-2 forward + layer-2 loss + Del-2 input gradient are ONE kernel (csrc/del_fused.hip)
-        self._fuse_l2 = (self._split2 and self.t1.folded and self.o in (32, 64) and self.t2.n_rows > 0
+        self._fuse_l2 = (self._mse and self._split2 and self.t1.folded and self.o in (32, 64) and self.t2.n_rows > 0
                          and os.environ.get('GD_NO_FUSED_L2') != '1')
         if self._fuse_l2:
             self._slot2, self._cnt_signed2 = _loss_slots(self.t2, self.idx2, self.s2, dev)
@@ -423,7 +534,7 @@ class NodeembEngine:
         # both layers, MFMA-able widths, a loss type whose layer-1 gradient feeds W_D1, every loss row inside S1
         self._fuse_loss1 = False
         t1 = self.t1
-        if (t1.folded and self.t2.folded and loss_type in ('both_layerwise', 'both_all', 'only1') and self.s1 > 0
+        if (self._mse and t1.folded and self.t2.folded and loss_type in ('both_layerwise', 'both_all', 'only1') and self.s1 > 0
                 and self.h in (32, 64, 128) and t1.n_rows > 0 and os.environ.get('GD_NO_FUSED_LOSS1') != '1'):
             pos = torch.searchsorted(self.idx1, t1.row_idx)
             inside = (pos < self.s1) & (self.idx1[pos.clamp(max=self.s1 - 1)] == t1.row_idx)
@@ -1134,10 +1245,11 @@ class NodeembEngine:
         k = min(self.steps_done, self.hist.shape[0])
         s = self.hist[:k].double().cpu()
         nan = float('nan')
-        r1 = (s[:, 0] + self.t1.k_const[0]) / self.t1.n_r if self.t1.count_r else s[:, 0] * nan
-        l1 = (s[:, 1] + self.t1.k_const[1]) / self.t1.n_l if self.t1.count_l else s[:, 1] * nan
-        r2 = (s[:, 2] + self.t2.k_const[0]) / self.t2.n_r if self.t2.count_r else s[:, 2] * nan
-        l2 = (s[:, 3] + self.t2.k_const[1]) / self.t2.n_l if self.t2.count_l else s[:, 3] * nan
+        fam = self.family
+        r1 = logged_loss(fam, s[:, 0], self.t1.k_const[0], self.t1.n_r) if self.t1.count_r else s[:, 0] * nan
+        l1 = logged_loss(fam, s[:, 1], self.t1.k_const[1], self.t1.n_l) if self.t1.count_l else s[:, 1] * nan
+        r2 = logged_loss(fam, s[:, 2], self.t2.k_const[0], self.t2.n_r) if self.t2.count_r else s[:, 2] * nan
+        l2 = logged_loss(fam, s[:, 3], self.t2.k_const[1], self.t2.n_l) if self.t2.count_l else s[:, 3] * nan
         a, lt = self.alpha, self.loss_type
         if lt in ('both_all', 'both_layerwise'):
             loss_r, loss_l = r1 + r2, l1 + l2

@@ -7,6 +7,8 @@ Two execution paths behind the same API:
     iteration - frozen-backbone forward, Del, Deleted-Edge-Consistency + Neighborhood-Influence
     losses, hand-derived backward, Adam - is gnndelete_amd.engine.NodeembEngine, one hipGraph
     replay per epoch, no per-step host sync;
+  * with --fused_row_losses the same engine runs --loss_fct kld_* / cosine_* (their terms folded per touched row,
+    gd_rowfold_loss_f32) where the request allows it;
   * generic path (any other loss function): autograd through the HIP-backed model with
     torch.optim.Adam, reproducing every --loss_type branch including its zero_grad placement.
 Both keep the update rules of gnndelete_nodeemb.py:215-299 and the model-selection /
@@ -200,6 +202,23 @@ class _EmbeddingUnlearner:
         return loss_name in ('mse_mean', 'mse_sum') and isinstance(conv2, (GCNConv, GATConv, GINConv, SAGEConv)) and \
             not (isinstance(conv2, GINConv) and conv2.nn.out_features > conv2.nn.in_features)
 
+    def _row_losses_unsupported(self, model, loss_name, args, pos_edge, ni1, ni2):
+        """None where --fused_row_losses can run this request on NodeembEngine, else the reason (one line)."""
+        if getattr(args, 'no_fused_step', False):
+            return '--no_fused_step is set'
+        if loss_name not in ('kld_mean', 'kld_sum', 'cosine_mean', 'cosine_sum'):
+            return f'no folded form of --loss_fct {loss_name} (kld_mean, kld_sum, cosine_mean, cosine_sum; mse_* run fused without the flag)'
+        if not self._can_fuse(model, 'mse_mean'):
+            return f'no fused step for the {type(model).__name__} backbone'
+        h, o = model.deletion1.deletion_weight.shape[0], model.deletion2.deletion_weight.shape[0]
+        from ...engine import padded_class_width
+        o_run = padded_class_width(h, o)            # (the engine pads a small class dimension; the kernel then sees that width)
+        if h % 4 or h > 128 or o_run % 4 or o_run > 128:
+            return f'hidden / output widths {h} / {o} are outside the folded row-loss kernel (multiples of 4 up to 128)'
+        if pos_edge.numel() and bool((ni1 | ni2)[pos_edge.flatten()].any()):
+            return 'a Neighborhood-Influence row is an endpoint of a deleted edge (the fold needs one kind of term per row)'
+        return None
+
     def _unlearn(self, model, data, optimizer, args, edge_key, loss_name, loss_type, select_best):
         _require_gpu()
         model = model.to(device)
@@ -215,12 +234,20 @@ class _EmbeddingUnlearner:
         ni1, ni2 = data.sdf_node_1hop_mask_non_df_mask, data.sdf_node_2hop_mask_non_df_mask
 
         engine = None
-        if self._can_fuse(model, loss_name) and not getattr(args, 'no_fused_step', False):
+        fuse = self._can_fuse(model, loss_name) and not getattr(args, 'no_fused_step', False)
+        if getattr(args, 'fused_row_losses', False) and loss_name not in ('mse_mean', 'mse_sum'):
+            reason = self._row_losses_unsupported(model, loss_name, args, pos_edge, ni1, ni2)
+            fuse = reason is None
+            if reason is not None:
+                print(f'--fused_row_losses: {reason}; running the autograd loop', flush=True)
+        if getattr(args, 'fused_row_losses', False):
+            self.trainer_log['nodeemb_step'] = 'fused' if fuse else 'autograd'
+        if fuse:
             from ...engine import NodeembEngine
             lr, betas, eps = _adam_hyper(optimizer)
             engine = NodeembEngine(model, data.x, e_sdf, z1_ori, z2_ori, pos_edge, neg_edge, ni1, ni2,
                                    loss_type=loss_type, alpha=self.args.alpha, lr=lr,
-                                   reduction='mean' if loss_name == 'mse_mean' else 'sum',
+                                   loss_fct=loss_name,
                                    history=max(16, args.epochs),
                                    cache_layer1=not getattr(args, 'no_layer1_cache', False),
                                    affected_rows_only=not getattr(args, 'all_rows', False))

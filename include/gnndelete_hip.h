@@ -45,7 +45,8 @@ extern "C" {
                                 AND an index list; the one-launch item kernels abort on a misaligned XCD range table instead of deadlocking;
                                 gd_induced_subgraph, gd_batch_csr, gd_batch_loss_terms (+ their _workspace queries): the GraphSAINT batch step;
                                 gd_edgeprob_dec_f32, gd_edge_incidence (+ their _workspace queries), gd_rows_add_f32, gd_edgeprob_record_f32:
-                                the fused edge-probability step (entries added, none changed: the version stays) */
+                                the fused edge-probability step (entries added, none changed: the version stays);
+                                gd_rowfold_loss_f32 (+ _blocks), gd_rowfold_kld_scale_f32: the folded KLD / cosine row losses (entries added: the version stays) */
 
 enum {
   GD_OK = 0,
@@ -616,6 +617,40 @@ int32_t gd_rowtarget_mse_blocks(int32_t n_rows);
 int gd_loss_finalize_f32(const float* partials1, int32_t n1, const float* partials2, int32_t n2,
                          const float* extra_sums, float* hist, int32_t capacity, int32_t* pos, int32_t* iter,
                          void* stream);
+
+/* The bounded-KLD and cosine-distance row losses of the loss zoo (see gd_rowpair_loss_f32) in the PRE-FOLDED form of
+ * gd_rowtarget_mse_f32, for full-batch runs whose targets never change.  All terms t of a touched row u (row_idx[u], targets
+ * o_t, cnt[u] = c of them, one kind per row: 0 = DEC, 1 = NI) are folded once by the caller, in fp64, into tm[u,:] ([n_rows, d]
+ * compact); with z = z[row_idx[u], :]:
+ *   family 0, cosine distance ((1 - cos(z, o)).mean() | .sum(), each norm clamped at 1e-8):   tm = U = sum_t o_t / max(|o_t|, 1e-8)
+ *       sum_t (1 - cos(z, o_t)) = c - <z, U> / max(|z|, 1e-8)                                   added to the sum of kind[u]
+ *       dz[row,:] = coef[u] * (-U / |z| + <z, U> z / |z|^3);  where |z| < 1e-8 the denominator is the constant: coef[u] * (-U / 1e-8)
+ *       coef[u] = coef_kind / n_kind (n = number of terms of the kind for _mean, 1 for _sum): the gradient is final.
+ *   family 1, bounded KLD (1 - exp(-kl_div(log_softmax(z), softmax(o), 'batchmean' | 'sum'))):   tm = T = sum_t softmax(o_t)
+ *       sum_t KL(softmax(o_t) || softmax(z)) = K_u + c KL(T / c || softmax(z)),
+ *           K_u = sum_t sum_j softmax(o_t)_j log softmax(o_t)_j - sum_j T_j log(T_j / c)  >= 0, a constant the caller keeps
+ *           (summed per kind: KL_kind = K_kind + sum_kind; written this way both parts are non-negative and nothing cancels)
+ *       c KL(T / c || softmax(z)) = sum_j T_j (log T_j - log c - log_softmax(z)_j)              added to the sum of kind[u]
+ *       dz[row,:] = coef[u] * (c softmax(z) - T),  coef[u] = coef_kind;  d loss_kind / d z = exp(-KL_kind / n_kind) / n_kind times
+ *       that, a scalar known only after the reduction: gd_rowfold_kld_scale_f32 multiplies it in (pass B).
+ * Softmax (stable: the row maximum is subtracted; expf / logf in fp32), dots and norms run over the first d_valid <= d columns
+ * only and dz is written as ZERO behind them (a class dimension padded with zero columns: a softmax over the padding would be
+ * another function).  d in [4, 128], d % 4 == 0; z and dz are pitched (ld >= d, ld % 4 == 0), only the d columns of the touched
+ * rows are written; row_idx need not be ascending.  partials: 2 floats per block (DEC, NI), gd_rowfold_loss_blocks(n_rows)
+ * blocks, the layout gd_loss_finalize_f32 / gd_step_tail_parts_f32 reduce.  dz = NULL: the sums only.  One pass: z read once,
+ * tm read once, dz written once; no atomics, the same bits every run. */
+int32_t gd_rowfold_loss_blocks(int32_t n_rows);
+int gd_rowfold_loss_f32(int32_t family, const float* z, int64_t ld_z, const float* tm, int32_t d, int32_t d_valid,
+                        const int32_t* row_idx, const float* coef, const float* cnt, const int32_t* kind, int32_t n_rows,
+                        float* dz, int64_t ld_dz, float* partials, void* stream);
+/* Pass B of the bounded KLD, on the device (no host read, no float atomics), two launches: one block adds the n_blocks =
+ * gd_rowfold_loss_blocks(n_rows) partial pairs of pass A up in a fixed order and stores
+ *       scales[kind] = exp(-(sum_kind + k_kind) * inv_n_kind) * inv_n_kind     (k = K_kind above, inv_n = 1 / n_kind, or 0: no terms)
+ * then a launch over the loss rows multiplies the d columns of dz[row_idx[u], :] by scales[kind[u]].  scales: 2 floats on the
+ * device (required).  dz = NULL: the scalars only. */
+int gd_rowfold_kld_scale_f32(const float* partials, int32_t n_blocks, float k_dec, float k_ni, float inv_n_dec, float inv_n_ni,
+                             const int32_t* row_idx, const int32_t* kind, int32_t n_rows, int32_t d, float* dz, int64_t ld_dz,
+                             float* scales, void* stream);
 
 /* Dense transform with a reduction dimension of any width: out[row(s), :] = in[row(s), :] @ W (+ bias), s < n_rows,
  * row(s) = idx[s] or s; in [*, k] with k % 32 == 0 (zero-pad the columns of `in` and the rows of W), W [k, n] row-major
