@@ -694,15 +694,32 @@ def test_rowtarget_mse_matches_direct_formula(d):
 
 
 @pytest.mark.parametrize('n,s,d,n_df', [(400, 300, 64, 40), (200, 70, 64, 10), (90, 90, 128, 0), (50, 33, 32, 5),
-                                        (40, 1, 64, 0), (40, 0, 64, 0), (60, 45, 20, 6), (3000, 2500, 64, 300)])
+                                        (40, 1, 64, 0), (40, 0, 64, 0), (60, 45, 20, 6), (3000, 2500, 64, 300),
+                                        (700, 530, 64, 40)])
 def test_pairs_sigmoid_mse_matches_oracle_pairs(n, s, d, n_df):
     """Edge-probability NI term (gnndelete.py:174-193, 239-241): the fused tile kernel against the
     oracle's explicit pair list in float64 - value and gradient - including a ragged last tile, a
-    single node, no node at all, excluded (Df) pairs and a feature width off the MFMA path."""
+    single node, no node at all, excluded (Df) pairs and a feature width off the MFMA path.
+    s = 530: 17 column tiles in 9 splits of two, the last split with one tile."""
+    _check_pairs_sigmoid_mse(n, s, d, n_df, 0.4)
+
+
+PAIRS_SATURATED_SCALE = 1.9
+
+
+def test_pairs_sigmoid_mse_with_saturated_pairs():
+    """The (200, 70, 64, 10) case with z scaled until the dot products reach about +-100: sigmoid is 0 or 1 to the last
+    bit for most pairs and exp() of the raw dot product would overflow.  Scale 1.9: dot products in [-99.7, 116.6], 1,306 of
+    the 2,405 pairs beyond +-17 (1 - sigmoid below fp32's epsilon).  Plain fp32 torch with the same formula is 3.8e-8 from
+    fp64 in the loss and 1.2e-6 (rel-L2) in the gradient, inside both bounds; the kernel on an MI355X: 1.5e-7 and 1.5e-6."""
+    _check_pairs_sigmoid_mse(200, 70, 64, 10, PAIRS_SATURATED_SCALE)
+
+
+def _check_pairs_sigmoid_mse(n, s, d, n_df, z_scale):
     from gnndelete_amd import ops
     from oracle import gnndelete_ref as R
     g = torch.Generator().manual_seed(n + s + d)
-    z = torch.randn(n, d, generator=g) * 0.4
+    z = torch.randn(n, d, generator=g) * z_scale
     mask = torch.zeros(n, dtype=torch.bool)
     mask[torch.randperm(n, generator=g)[:s]] = True
     nodes = mask.nonzero().flatten()
@@ -728,6 +745,9 @@ def test_pairs_sigmoid_mse_matches_oracle_pairs(n, s, d, n_df):
     if count == 0:
         assert float(got) == 0.0 and float(zg.grad.abs().max()) == 0.0
         return
+    print(f'pairs n={n} s={s} d={d} z_scale={z_scale}: loss rel {abs(float(got) - float(want)) / abs(float(want)):.2e}  '
+          f'gradient rel_l2 {rel_l2(zg.grad.cpu() / 3.0, zd.grad):.2e}')
+    assert bool(torch.isfinite(got)) and bool(torch.isfinite(zg.grad).all())
     assert abs(float(got) - float(want)) <= 1e-5 * abs(float(want))
     assert rel_l2(zg.grad.cpu() / 3.0, zd.grad) < TOL
     assert torch.all(zg.grad.cpu()[~mask] == 0)
