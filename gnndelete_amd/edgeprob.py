@@ -18,6 +18,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import check, ptr, stream_ptr
+from .capture import capture_iterations
 
 
 def fused_edgeprob_unsupported(model, args, optimizer):
@@ -210,20 +211,7 @@ class EdgeprobEngine:
         return state
 
     def _capture(self):
-        saved = [t.clone() for t in self._mutable_state()]
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._iteration()                      # warm-up (allocator, code objects, the plans' cached work items)
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self._iteration()
-        graph.replay()                             # first launch = upload of the exec; on scratch state
-        torch.cuda.synchronize()
-        for t, s in zip(self._mutable_state(), saved):
-            t.copy_(s)                             # undo the warm-up iterations
-        self._graph = graph
+        self._graph = capture_iterations(self._iteration, self._mutable_state)
 
     # ---------------------------------------------------------------------------------------------- public
     def step(self, neg):

@@ -23,17 +23,135 @@ Per-step loss sums are appended to a device-side history without a host sync.
 With loss_fct = kld_* / cosine_* (--fused_row_losses) the loss stage of each layer is the folded row-loss launch
 (gd_rowfold_loss_f32, for the bounded KLD followed by gd_rowfold_kld_scale_f32) between the Del row product and the
 weight-gradient launch; the forms that fuse the MSE loss into a neighbouring kernel are off, the rest of the step is the same.
+
+Which launches a step makes is decided in three phases when the engine is built.  FACTS: everything the decision depends on -
+backbone, loss, widths, row counts, the set relations between loss rows, Del rows and the graph, the library's two coverage
+predicates - is gathered from the request into a StepFacts record.  KNOBS: read_knobs() reads every GD_* variable this module
+consults, once per construction.  FORMS: plan_step(facts, knobs) - a pure function of the two records, no tensors, no library
+calls - returns the StepForms the constructor then acts on in one pass (loss rows reordered, every buffer allocated once).
 """
 import os
+import warnings
+from typing import NamedTuple
 
 import torch
 
 from . import _lib, ops
 from ._lib import check, ptr, stream_ptr
+from .capture import capture_iterations
 from .graph import graph_for
 from .nn import GATConv, GCNConv, GINConv, RGCNConv, SAGEConv
 
 LOSS_TYPES = ('both_all', 'both_layerwise', 'only2_layerwise', 'only2_all', 'only1')
+
+
+class StepFacts(NamedTuple):
+    """What plan_step decides from; computed from the request before any form is chosen."""
+    mode: str                 # 'gcn' | 'gin' | 'gat' | 'sage' | 'rgcn'
+    loss_type: str
+    family: str               # 'mse' | 'kld' | 'cosine'
+    h: int
+    o: int
+    s1: int                   # Del-1 / Del-2 rows
+    s2: int
+    folded1: bool             # per layer: one kind of loss term per row (the folded loss form),
+    n_rows1: int              # its loss rows (0 where not folded),
+    inside1: bool             # and whether all of them are Del rows (_rows_inside)
+    folded2: bool
+    n_rows2: int
+    inside2: bool
+    cache_layer1: bool
+    rows_only_asked: bool     # affected_rows_only as the caller passed it
+    closed: bool              # asked, not R-GCN, and the S2 / S1 row sets are closed under the graph
+    w2_mfma: bool             # conv2's weight fits the matrix-core row kernel's LDS image
+    gin_ok: bool              # GIN whose layers do not widen their input
+    del1_covers: bool         # gd_del1_loss_wgrad_covers(s1, h)
+    pair_covers: bool         # gd_rowtarget_mse_pair_covers(h, o)
+
+
+class Knobs(NamedTuple):
+    """The GD_* environment variables of this module (field = variable name without GD_, lower case)."""
+    no_split_loss: bool = False
+    no_split: bool = False
+    no_fused_l2: bool = False
+    cache_split: bool = True              # (GD_CACHE_SPLIT=0 turns it off; likewise the other two that default to on)
+    no_fused_loss1: bool = False
+    no_step_tail: bool = False
+    tail_fused_only: bool = False
+    no_fused_wgrad2: bool = False
+    del1_chain: bool = True
+    no_gat_rank1_epilogue: bool = False
+    no_loss_pair: bool = False
+    no_gat_dots: bool = False
+    rgcn_reorder: bool = True
+    rgcn_node_major: bool = False
+    rgcn_relu_pass: bool = False
+    sage_root_in_spmm: bool = False
+    pad_out: int = 64
+
+
+def read_knobs(env=None):
+    env = os.environ if env is None else env
+    val = {}
+    for name, default in Knobs._field_defaults.items():
+        raw = env.get('GD_' + name.upper())
+        if name == 'pad_out':
+            try:
+                val[name] = default if raw is None else int(raw)
+            except ValueError:
+                warnings.warn(f'GD_PAD_OUT={raw!r} is not an integer: the class dimension is not padded')
+                val[name] = 0
+        else:
+            val[name] = (raw != '0') if default else (raw == '1')
+    return Knobs(**val)
+
+
+class StepForms(NamedTuple):
+    """The kernel forms of a step (the engine carries each as the attribute `_<field>`)."""
+    split1: bool              # conv1 writes pre1, Del-1 writes z1[S1] out of place
+    split2: bool              # the same for layer 2 (p2 / z2)
+    out1: bool                # this layer's loss rows OUTSIDE the Del rows get a launch of their own
+    out2: bool
+    fuse_loss1: bool          # layer-1 loss inside the W_D1 weight-gradient fetch
+    fuse_l2: bool             # Del-2 forward + layer-2 loss + Del-2 input gradient in one kernel
+    tail: bool                # both split-K reductions + Adam + loss finalize in one launch
+    fuse_wg2: bool            # the W_D2 weight gradient's partial sums come out of the fused Del-2 kernel
+    fuse_del1: bool           # Del-1 + layer-1 loss + W_D1 weight gradient in one pass
+    chain1: bool              # ... which also forms the gradient conv2 sent back in the previous iteration
+    out_pair: bool            # the two outside-row loss launches are one
+    rows_only: bool           # every N-row kernel runs on the affected rows
+    rgcn_rows_only: bool      # R-GCN: conv2's input gradient on the Del-1 rows only
+    gat_dots: bool            # GAT attention logits from the GEMM epilogue
+
+
+def plan_step(facts, k):
+    """StepForms of a request with these StepFacts under the Knobs k.  Pure: the comments on each form are with the kernels
+    it selects, in NodeembEngine.__init__ and _iteration."""
+    (mode, loss_type, family, h, o, s1, s2, folded1, n_rows1, inside1, folded2, n_rows2, inside2, cache_layer1, rows_only_asked,
+     closed, w2_mfma, gin_ok, del1_covers, pair_covers) = facts
+    mse = family == 'mse'
+    # loss rows outside the Del rows (knowledge graphs): the fused forms take the rows inside, one stand-alone launch the rest
+    mixed_ok = folded1 and folded2 and not k.no_split_loss and not k.no_split
+    out2 = not inside2 and mixed_ok and mse and s2 > 0 and o in (32, 64) and n_rows2 > 0 and not k.no_fused_l2
+    split2 = (inside2 or out2) and not k.no_split
+    fuse_l2 = mse and split2 and folded1 and o in (32, 64) and n_rows2 > 0 and not k.no_fused_l2
+    split1 = (not cache_layer1 or k.cache_split) and inside1 and not k.no_split
+    loss1_ok = (mse and folded1 and folded2 and loss_type in ('both_layerwise', 'both_all', 'only1') and s1 > 0
+                and h in (32, 64, 128) and n_rows1 > 0 and not k.no_fused_loss1)
+    out1 = loss1_ok and not inside1 and mixed_ok            # (not inside1 implies not split1)
+    fuse_loss1 = loss1_ok and (inside1 or out1)
+    tail = (folded1 and folded2 and s1 > 0 and s2 > 0 and loss_type in ('both_layerwise', 'both_all') and h % 2 == 0 and o % 2 == 0
+            and not k.no_step_tail
+            and ((fuse_loss1 and fuse_l2) or (h in (32, 64, 128) and o in (32, 64, 128) and not k.tail_fused_only)))
+    fuse_wg2 = tail and fuse_l2 and not k.no_fused_wgrad2
+    fuse_del1 = tail and fuse_loss1 and split1 and loss_type in ('both_layerwise', 'only1') and del1_covers
+    chain1 = (fuse_del1 and loss_type == 'both_layerwise' and h == 128 and o == 64 and k.del1_chain
+              and (mode in ('gcn', 'gin') or (mode == 'gat' and w2_mfma and not k.no_gat_rank1_epilogue)))
+    out_pair = out1 and out2 and fuse_loss1 and fuse_l2 and loss_type != 'only2_all' and pair_covers and not k.no_loss_pair
+    rows_only = (rows_only_asked and (mode in ('gcn', 'gat', 'sage') or gin_ok) and split2 and s2 > 0
+                 and not out1 and not out2 and closed)     # (loss rows outside the Del rows read conv outputs of rows outside S2)
+    return StepForms(split1, split2, out1, out2, fuse_loss1, fuse_l2, tail, fuse_wg2, fuse_del1, chain1, out_pair, rows_only,
+                     rows_only_asked and mode == 'rgcn', not k.no_gat_dots)
 
 
 def _loss_coefficients(loss_type, alpha):
@@ -87,6 +205,12 @@ def logged_loss(family, raw_sum, k_const, n):
     mse (s + K) / n;  cosine s / n (the kernel adds up 1 - cos itself, K = 0);  kld 1 - exp(-(s + K) / n)."""
     v = (raw_sum + k_const) / n
     return 1.0 - torch.exp(-v) if family == 'kld' else v
+
+
+def _members(idx, n_sel, rows):
+    """(is each entry of `rows` in the sorted list idx[:n_sel] (n_sel > 0), its position there)."""
+    pos = torch.searchsorted(idx, rows)
+    return (pos < n_sel) & (idx[pos.clamp(max=n_sel - 1)] == rows), pos
 
 
 class _LayerTerms:
@@ -186,6 +310,8 @@ class _LayerTerms:
             self.z_ori = z_ori
             ws = _lib.lib().gd_rowpair_mse_workspace(self.n_seg)
         self.partials = torch.zeros(max(2, ws), dtype=torch.float32, device=device)
+        if self.folded:
+            self.n_in = self.n_rows                 # loss rows inside the Del rows (order_inside_first: the others go behind them)
 
     def n_partial_blocks(self):
         """Blocks of per-block loss partials the folded kernel writes (for gd_loss_finalize_f32)."""
@@ -201,8 +327,7 @@ class _LayerTerms:
         if self.n_rows == 0 or n_sel == 0:
             self.n_in = 0 if n_sel == 0 else self.n_rows
             return self.n_in
-        pos = torch.searchsorted(idx, self.row_idx)
-        inside = (pos < n_sel) & (idx[pos.clamp(max=n_sel - 1)] == self.row_idx)
+        inside, _ = _members(idx, n_sel, self.row_idx)
         order = torch.argsort((~inside).to(torch.int8), stable=True)
         self.row_idx, self.cnt = self.row_idx[order].contiguous(), self.cnt[order].contiguous()
         self.coef, self.kind = self.coef[order].contiguous(), self.kind[order].contiguous()
@@ -211,7 +336,7 @@ class _LayerTerms:
         return self.n_in
 
     def outside_blocks(self):
-        n_out = self.n_rows - getattr(self, 'n_in', self.n_rows)
+        n_out = self.n_rows - self.n_in
         return _lib.lib().gd_rowtarget_mse_blocks(n_out) if n_out else 0
 
     def launch_outside(self, z, dz, partials):
@@ -295,16 +420,14 @@ def _rows_inside(terms, idx, n_sel):
         return False
     if terms.n_rows == 0:
         return True
-    pos = torch.searchsorted(idx, terms.row_idx)
-    return bool(((pos < n_sel) & (idx[pos.clamp(max=n_sel - 1)] == terms.row_idx)).all())
+    return bool(_members(idx, n_sel, terms.row_idx)[0].all())
 
 
 def _loss_slots(terms, idx, n_sel, device):
     """(slot[n_sel] int32: position of each Del row in the folded loss rows or -1, cnt with NI negative)."""
     slot = torch.full((n_sel,), -1, dtype=torch.int32, device=device)
     if terms.n_rows:
-        pos = torch.searchsorted(idx, terms.row_idx)
-        inside = (pos < n_sel) & (idx[pos.clamp(max=n_sel - 1)] == terms.row_idx)      # (loss rows outside the Del rows: no slot)
+        inside, pos = _members(idx, n_sel, terms.row_idx)      # (loss rows outside the Del rows: no slot)
         slot[pos[inside]] = torch.arange(terms.n_rows, dtype=torch.int32, device=device)[inside]
     return slot, torch.where(terms.kind == 1, -terms.cnt, terms.cnt).contiguous()
 
@@ -357,10 +480,10 @@ def _padded_out_shadow(model, o_pad):
     return SimpleNamespace(conv1=model.conv1, conv2=s2.to(dev), deletion1=model.deletion1, deletion2=del2)
 
 
-def padded_class_width(h, o, rgcn=False):
+def padded_class_width(h, o, rgcn=False, knobs=None):
     """The layer-2 width NodeembEngine runs a model of hidden width h and output width o at: a class dimension below 32 is padded
-    to GD_PAD_OUT (32 | 64, default 64; 0 = off) where h = 128, every other width stays."""
-    pad_to = int(os.environ.get('GD_PAD_OUT', '64'))
+    to GD_PAD_OUT (32 | 64, default 64; 0 or not a number = off) where h = 128, every other width stays."""
+    pad_to = (knobs or read_knobs()).pad_out
     return pad_to if (not rgcn and o < 32 and pad_to in (32, 64) and h == 128) else o
 
 
@@ -385,9 +508,9 @@ class NodeembEngine:
             raise ValueError(f'NodeembEngine: no fused step for loss_fct={loss_fct!r} (one of {sorted(LOSS_FAMILIES)})')
         self.loss_fct = loss_fct
         self.family, reduction = LOSS_FAMILIES[loss_fct]
-        self._mse = self.family == 'mse'
+        self.knobs = knobs = read_knobs()
         conv1, conv2 = model.conv1, model.conv2
-        if not self._mse and isinstance(conv2, RGCNConv):
+        if self.family != 'mse' and isinstance(conv2, RGCNConv):
             raise NotImplementedError('NodeembEngine: the folded KLD / cosine losses are not wired into the R-GCN step')
         if not isinstance(conv2, (GCNConv, GINConv, GATConv, SAGEConv, RGCNConv)):
             raise NotImplementedError(f'NodeembEngine: unsupported conv {type(conv2).__name__}')
@@ -401,12 +524,7 @@ class NodeembEngine:
             # conv's fabric reads by ~10 % (FETCH_SIZE 4.41 -> 3.95 GB per layer-1 launch, profiles/r03_rgcn_reorder_ab.txt).
             # With the tile kernel that bought nothing (bound by its per-step dependent chain); the wave-private kernel runs
             # at the fabric rate, where bytes are time: 2.01 -> 1.89 ms per step on the synth-biokg request (round 4).
-            # (cache_layer1: as for the other backbones - conv1's output is loop-invariant; affected_rows_only: conv2's INPUT
-            #  GRADIENT is formed for the Del-1 rows only, the only rows that read it - see _conv2_backward_to_s1; the forward
-            #  stays whole: the DEC rows of a knowledge-graph request are the Df endpoints, most of the graph)
-            self._rgcn_rows_only = bool(affected_rows_only)
-            affected_rows_only = False
-            reorder = os.environ.get('GD_RGCN_REORDER', '1') != '0'
+            reorder = knobs.rgcn_reorder
             x = model.node_emb.weight.detach()[x.to(model.node_emb.weight.device)]      # frozen embedding lookup, once
         dev = x.device
         if dev.type != 'cuda':
@@ -416,7 +534,7 @@ class NodeembEngine:
         # W_D2's top-left block is copied back into the caller's parameter at the end of every iteration.
         self._o_true = int(model.deletion2.deletion_weight.shape[0])
         self._user_wd2 = None
-        pad_to = padded_class_width(model.deletion1.deletion_weight.shape[0], self._o_true, isinstance(conv2, RGCNConv))
+        pad_to = padded_class_width(model.deletion1.deletion_weight.shape[0], self._o_true, isinstance(conv2, RGCNConv), knobs)
         if pad_to != self._o_true:
             self._user_wd2 = model.deletion2.deletion_weight
             model = _padded_out_shadow(model, pad_to)
@@ -459,47 +577,71 @@ class NodeembEngine:
         self.needs_l2_to_w1 = loss_type in ('both_all', 'both_layerwise', 'only2_all')
 
         f32 = dict(dtype=torch.float32, device=dev)
-        self.z1 = torch.empty(n, self.h, **f32)
-        self.z2 = torch.empty(n, self.o, **f32)
-        self.xs1 = torch.empty(max(1, self.s1), self.h, **f32)       # p1[S1] (input rows of Del-1)
+        self._mode = {GCNConv: 'gcn', GINConv: 'gin', GATConv: 'gat', SAGEConv: 'sage', RGCNConv: 'rgcn'}[type(conv2)]
+        self.graph = None
+        if self._mode != 'rgcn':
+            self.graph = graph_for(edge_index, n, {'gcn': 'gcn', 'gin': 'sum', 'gat': 'gat', 'sage': 'mean'}[self._mode])
+        # ---- phase 1: the facts
+        w2 = {'gcn': lambda: conv2.lin.weight, 'gin': lambda: conv2.nn.weight, 'gat': lambda: conv2.lin_src.weight,
+              'sage': lambda: conv2.lin_l.weight, 'rgcn': lambda: None}[self._mode]()
+        rows_only_asked = bool(affected_rows_only)
+        self.facts = StepFacts(
+            mode=self._mode, loss_type=loss_type, family=self.family, h=self.h, o=self.o, s1=self.s1, s2=self.s2,
+            folded1=self.t1.folded, n_rows1=self.t1.n_rows if self.t1.folded else 0, inside1=_rows_inside(self.t1, self.idx1, self.s1),
+            folded2=self.t2.folded, n_rows2=self.t2.n_rows if self.t2.folded else 0, inside2=_rows_inside(self.t2, self.idx2, self.s2),
+            cache_layer1=bool(cache_layer1), rows_only_asked=rows_only_asked,
+            closed=rows_only_asked and self._mode != 'rgcn' and self.s2 > 0 and self._affected_rows_closed(),
+            w2_mfma=w2 is not None and self._mfma_weight(w2),
+            gin_ok=(self._mode == 'gin' and conv1.nn.out_features <= conv1.nn.in_features
+                    and conv2.nn.out_features <= conv2.nn.in_features),
+            del1_covers=bool(_lib.lib().gd_del1_loss_wgrad_covers(self.s1, self.h)),
+            pair_covers=bool(_lib.lib().gd_rowtarget_mse_pair_covers(self.h, self.o)))
+        # ---- phase 2: the forms, each carried as the attribute `_<name>` (what _iteration, bench.py and the tests read)
+        self.forms = plan_step(self.facts, knobs)
+        for name, on in self.forms._asdict().items():
+            setattr(self, '_' + name, on)
+        # ---- phase 3: act on them
+        lib = _lib.lib()
         # Del-2 out of place: conv2 writes p2, Del-2 writes z2[S2] from p2[S2] and the weight gradient gathers its
         # operand from p2 - no [S2, O] copy of the Del input per step.  z2 rows outside S2 are then never
         # formed, which training only tolerates when every layer-2 loss row lies in S2 (always so for the
         # reference's masks); otherwise the in-place form with its saved input is used.
         # (round 5) Knowledge-graph requests: upstream hands the NI masks to the Del operators (S minus the Df endpoints), so the
         # DEC rows lie OUTSIDE the Del rows.  The fused forms then take the loss rows inside the Del rows (the NI rows) and one
-        # stand-alone loss launch per layer the rest, reading the conv output (Del is the identity there): layer 2 writes their
-        # dz2 rows (= dp2, conv2's backward reads them), layer 1 the loss sums only (no trainable weight lies upstream of them).
-        self._out1 = self._out2 = 0
-        mixed_ok = (self.t1.folded and self.t2.folded and os.environ.get('GD_NO_SPLIT_LOSS') != '1' and os.environ.get('GD_NO_SPLIT') != '1')
-        inside2 = _rows_inside(self.t2, self.idx2, self.s2)
-        if (not inside2 and mixed_ok and self._mse and self.s2 > 0 and self.o in (32, 64) and self.t2.n_rows > 0
-                and os.environ.get('GD_NO_FUSED_L2') != '1'):
-            self._out2 = self.t2.n_rows - self.t2.order_inside_first(self.idx2, self.s2)
-            inside2 = True
-        self._split2 = inside2 and os.environ.get('GD_NO_SPLIT') != '1'
+        # stand-alone loss launch per layer the rest (_out1 / _out2), reading the conv output (Del is the identity there): layer 2
+        # writes their dz2 rows (= dp2, conv2's backward reads them), layer 1 the loss sums only (no trainable weight lies upstream
+        # of them).  _out_pair: the two stand-alone launches are one.
+        if self._out2:
+            self.t2.order_inside_first(self.idx2, self.s2)
+        if self._out1:
+            self.t1.order_inside_first(self.idx1, self.s1)
+        self.z1 = torch.empty(n, self.h, **f32)
+        self.z2 = torch.empty(n, self.o, **f32)
         self.p2 = torch.empty(n, self.o, **f32) if self._split2 else self.z2
         self.xs2 = None if self._split2 else torch.empty(max(1, self.s2), self.o, **f32)
-        # ... and with that, Del-2 forward + layer-2 loss + Del-2 input gradient are ONE kernel (csrc/del_fused.hip)
-        self._fuse_l2 = (self._mse and self._split2 and self.t1.folded and self.o in (32, 64) and self.t2.n_rows > 0
-                         and os.environ.get('GD_NO_FUSED_L2') != '1')
+        # ... and with that, Del-2 forward + layer-2 loss + Del-2 input gradient are ONE kernel (_fuse_l2, csrc/del_fused.hip);
+        # with the tail launch doing the reduction, the W_D2 weight gradient's partial sums come out of that kernel too
+        # (_fuse_wg2, gd_del_loss_bwd_wgrad_f32: p2 and dz2 are in its registers) - no weight-gradient launch, no dz2 buffer
+        self._lp1 = self._lp2 = None
+        self._lp1_blocks = self._lp2_blocks = 0
         if self._fuse_l2:
             self._slot2, self._cnt_signed2 = _loss_slots(self.t2, self.idx2, self.s2, dev)
-            self._lp2_blocks = _lib.lib().gd_del_loss_bwd_blocks(self.s2)
-            self._lp2 = torch.zeros(2 * max(1, self._lp2_blocks + self.t2.outside_blocks()), **f32)
+            if self._fuse_wg2:       # (one partial matrix per compute unit in the step-sized form; the buffer keeps the weight-gradient launch's size)
+                self._lp2_blocks = lib.gd_del_loss_bwd_wgrad_parts(self.s2, self.o)
+                lp2_size = lib.gd_rows_gemm_wgrad_blocks(self.s2)
+            else:
+                self._lp2_blocks = lp2_size = lib.gd_del_loss_bwd_blocks(self.s2)
+            self._lp2 = torch.zeros(2 * max(1, lp2_size + self.t2.outside_blocks()), **f32)
             self.dz2c = torch.zeros(self.s2, self.o, **f32)          # dz2 on the S2 rows (compact)
-        # Same for layer 1: conv1 writes pre1, Del-1 writes z1[S1] from pre1[S1]; conv2's Linear reads row r from z1 if r is in
-        # S1, else from pre1 (gd_rows_gemm_select_f32).  Upstream clones the whole [N, H] matrix for this (deletion.py:24).
+        # Same for layer 1 (_split1): conv1 writes pre1, Del-1 writes z1[S1] from pre1[S1]; conv2's Linear reads row r from z1 if r
+        # is in S1, else from pre1 (gd_rows_gemm_select_f32).  Upstream clones the whole [N, H] matrix for this (deletion.py:24).
         # (round 6) Also with the cached layer-1 output - pre1 is then that fixed buffer, filled once - so that the trainer's
         # default step runs the same fused / chained Del-1 pass as the full step instead of three launches (Del-1, the loss-fused
         # weight gradient, the gated product); GD_CACHE_SPLIT=0: the round-5 form (z1 = a copy of the cached output whose S1 rows
         # are overwritten every step).
-        self._split1 = ((not cache_layer1 or os.environ.get('GD_CACHE_SPLIT', '1') != '0')
-                        and _rows_inside(self.t1, self.idx1, self.s1) and os.environ.get('GD_NO_SPLIT') != '1')
         self.pre1 = torch.empty(n, self.h, **f32) if self._split1 else self.z1
         self._sel1 = m1.to(torch.uint8).contiguous() if self._split1 else None
-        if self._split1:
-            self.xs1 = None
+        self.xs1 = None if self._split1 else torch.empty(max(1, self.s1), self.h, **f32)       # p1[S1] (input rows of Del-1)
         self.dz1 = torch.zeros(n, self.h, **f32)                     # only loss rows are ever written
         if isinstance(conv2, SAGEConv):
             # [ dt2 = A_mean^T dp2 | dp2 ]: the two halves of conv2's input gradient operand side by side, so
@@ -513,170 +655,101 @@ class NodeembEngine:
         self.g1 = torch.zeros_like(self.wd1)                         # the .grad of W_D1 / W_D2
         self.g2 = torch.zeros_like(self.wd2)
         self.sums = torch.zeros(4, **f32)                            # r1, l1, r2, l2 (sums of squares)
-        self.ws1 = torch.empty(max(1, _lib.lib().gd_rows_gemm_wgrad_workspace(self.s1, self.h, self.h)), **f32)
-        self.ws2 = torch.empty(max(1, _lib.lib().gd_rows_gemm_wgrad_workspace(self.s2, self.o, self.o)), **f32)
+        self.ws1 = torch.empty(max(1, lib.gd_rows_gemm_wgrad_workspace(self.s1, self.h, self.h)), **f32)
+        self.ws2 = torch.empty(max(1, lib.gd_rows_gemm_wgrad_workspace(self.s2, self.o, self.o)), **f32)
         self.iter_ctr = torch.zeros(1, dtype=torch.int32, device=dev)       # advanced once per step
         self.adam1, self.adam2 = _Adam(self.wd1, lr, iter_ctr=self.iter_ctr), _Adam(self.wd2, lr, iter_ctr=self.iter_ctr)
         self.hist = torch.zeros(history, 4, **f32)
         self.hist_pos = torch.zeros(1, dtype=torch.int32, device=dev)
         self.steps_done = 0
-        self._graph = None
+        self._graph = self._graph_k = None
         self._use_graph = use_graph
         self._const_refs = {}
-        # OPT-IN (GD_SIDE_STREAM=1), measured and NOT kept as the default: the split-K reductions (+ Adam) and the loss
-        # finalize are launch-sized and nothing later in the iteration reads what they write, so they can run on a side
-        # stream, forked behind the kernel that feeds them and joined at the end of the iteration.  On this part the
-        # cross-queue dependencies of the replayed hipGraph cost more than the three links they remove from the chain:
-        # 683 -> 715 us per step (profiles/r03_ab.txt).
-        self._overlap = os.environ.get('GD_SIDE_STREAM') == '1'
-        self._side = torch.cuda.Stream(device=dev) if self._overlap else None
-        # layer-1 loss folded into the W_D1 weight-gradient fetch (see _wgrad1): needs the folded loss form on
-        # both layers, MFMA-able widths, a loss type whose layer-1 gradient feeds W_D1, every loss row inside S1
-        self._fuse_loss1 = False
-        t1 = self.t1
-        if (self._mse and t1.folded and self.t2.folded and loss_type in ('both_layerwise', 'both_all', 'only1') and self.s1 > 0
-                and self.h in (32, 64, 128) and t1.n_rows > 0 and os.environ.get('GD_NO_FUSED_LOSS1') != '1'):
-            pos = torch.searchsorted(self.idx1, t1.row_idx)
-            inside = (pos < self.s1) & (self.idx1[pos.clamp(max=self.s1 - 1)] == t1.row_idx)
-            if not bool(inside.all()) and mixed_ok and not self._split1:
-                self._out1 = t1.n_rows - t1.order_inside_first(self.idx1, self.s1)
-            if bool(inside.all()) or self._out1:
-                self._slot1, self._cnt_signed1 = _loss_slots(t1, self.idx1, self.s1, dev)
-                self._lp1_blocks = _lib.lib().gd_rows_gemm_wgrad_blocks(self.s1)
-                self._lp1 = torch.zeros(2 * max(1, self._lp1_blocks + t1.outside_blocks()), **f32)
-                self._fuse_loss1 = True
-        # The launch-sized tail of the step (two split-K reductions with Adam + the loss finalize) as ONE launch
+        # _fuse_loss1: the layer-1 loss folded into the W_D1 weight-gradient fetch (see _wgrad1): needs the folded loss form on
+        # both layers, MFMA-able widths, a loss type whose layer-1 gradient feeds W_D1, every loss row inside S1 (or _out1)
+        if self._fuse_loss1:
+            self._slot1, self._cnt_signed1 = _loss_slots(self.t1, self.idx1, self.s1, dev)
+            # (round 5) _fuse_del1: where the W_D1 step of an iteration only waits for gradients that exist when Del-1 runs (the
+            # layer-wise types: this iteration's layer-1 loss + the gradient conv2 sent back in the PREVIOUS one), Del-1 itself,
+            # the layer-1 loss and the W_D1 weight gradient are ONE pass over the S1 rows (gd_del1_loss_wgrad_f32: pre1 read once,
+            # z1 only written - the weight-gradient launch re-read both).  It leaves one partial matrix per compute unit (the
+            # tail launch is told how many); the buffer keeps the size of the two-launch form: bench.py's stand-alone timing of
+            # the weight-gradient kernel writes gd_rows_gemm_wgrad_blocks(s1) block sums into it
+            self._lp1_blocks = lib.gd_del1_loss_wgrad_parts(self.s1) if self._fuse_del1 else lib.gd_rows_gemm_wgrad_blocks(self.s1)
+            self._lp1 = torch.zeros(2 * max(1, lib.gd_rows_gemm_wgrad_blocks(self.s1) + self.t1.outside_blocks()), **f32)
+        # _tail: the launch-sized tail of the step (two split-K reductions with Adam + the loss finalize) as ONE launch
         # (gd_step_tail_f32) where both optimizers step in every iteration and both layers run their fused loss forms
         # (round 5: also where a layer runs its UNFUSED loss / weight-gradient stages - the knowledge-graph request, whose
         #  DEC rows lie outside the Del masks: the weight-gradient launches then leave their partial products, the loss kernels
-        #  their per-block partials, and four launch-sized kernels - two reductions, Adam, finalize - become this one)
-        self._tail = (t1.folded and self.t2.folded and self.s1 > 0 and self.s2 > 0
-                      and loss_type in ('both_layerwise', 'both_all') and not self._overlap and self.h % 2 == 0 and self.o % 2 == 0
-                      and os.environ.get('GD_NO_STEP_TAIL') != '1'
-                      and ((self._fuse_loss1 and self._fuse_l2)
-                           # (unfused stages: only where the weight-gradient launches are the split-K matrix kernels, whose partial
-                           #  products the tail reduces - widths of 32 / 64 / 128)
-                           or (self.h in (32, 64, 128) and self.o in (32, 64, 128) and os.environ.get('GD_TAIL_FUSED_ONLY') != '1')))
+        #  their per-block partials, and four launch-sized kernels - two reductions, Adam, finalize - become this one; only where
+        #  the weight-gradient launches are the split-K matrix kernels, whose partial products the tail reduces - widths of
+        #  32 / 64 / 128)
         self._tail_acc = [0, 0]
         self._arrive = torch.zeros(2, dtype=torch.int32, device=dev)     # step_tail's check-in counter (+ the word its address trick may name)
-        # ... and with the tail launch doing the reduction, the W_D2 weight gradient's partial sums come out of the fused Del-2
-        # kernel itself (gd_del_loss_bwd_wgrad_f32: p2 and dz2 are in its registers) - no weight-gradient launch, no dz2 buffer
-        self._fuse_wg2 = self._tail and self._fuse_l2 and os.environ.get('GD_NO_FUSED_WGRAD2') != '1'
-        if self._fuse_wg2:
-            self._lp2 = torch.zeros(2 * max(1, _lib.lib().gd_rows_gemm_wgrad_blocks(self.s2) + self.t2.outside_blocks()), **f32)
-            self._lp2_blocks = _lib.lib().gd_del_loss_bwd_wgrad_parts(self.s2, self.o)      # (one per compute unit in the step-sized form)
-        # (round 5) ... and where the W_D1 step of an iteration only waits for gradients that exist when Del-1 runs (the
-        # layer-wise types: this iteration's layer-1 loss + the gradient conv2 sent back in the PREVIOUS one), Del-1 itself, the
-        # layer-1 loss and the W_D1 weight gradient are ONE pass over the S1 rows (gd_del1_loss_wgrad_f32: pre1 read once, z1
-        # only written - the weight-gradient launch re-read both)
-        self._fuse_del1 = bool(self._tail and self._fuse_loss1 and self._split1 and loss_type in ('both_layerwise', 'only1')
-                               and _lib.lib().gd_del1_loss_wgrad_covers(self.s1, self.h))
-        if self._fuse_del1:       # ... which leaves one partial matrix per compute unit (the tail launch is told how many)
-            # (the buffer keeps the size of the two-launch form: bench.py's stand-alone timing of the weight-gradient kernel
-            #  writes gd_rows_gemm_wgrad_blocks(s1) block sums into it)
-            self._lp1_blocks = _lib.lib().gd_del1_loss_wgrad_parts(self.s1)
-        # ... and for GCN / GIN the gradient conv2 sent back in the previous iteration is FORMED in that pass too, from the aggregated
-        # layer-2 gradient the previous iteration left and the sign pattern its Del-1 stored (gd_del1_chain_loss_wgrad_f32): the
-        # gated [S1, 64] x [64, 128] product at the end of the step, its [S1, 128] write and the read-back are gone
-        self._chain1 = bool(self._fuse_del1 and loss_type == 'both_layerwise' and isinstance(conv2, (GCNConv, GINConv))
-                            and self.h == 128 and self.o == 64 and os.environ.get('GD_DEL1_CHAIN') != '0')
-        # (GATConv: the same with its two rank-1 terms added in front of the gate; the message gradient and the two logit gradients the
-        #  previous iteration's backward left live in buffers this engine owns)
-        self._gat_bufs = None
-        if (self._fuse_del1 and loss_type == 'both_layerwise' and isinstance(conv2, GATConv) and self.h == 128 and self.o == 64
-                and self._mfma_weight(conv2.lin_src.weight) and os.environ.get('GD_NO_GAT_RANK1_EPILOGUE') != '1'
-                and os.environ.get('GD_DEL1_CHAIN') != '0'):
-            self._chain1 = True
+        # _chain1: for GCN / GIN the gradient conv2 sent back in the previous iteration is FORMED in the Del-1 pass too, from the
+        # aggregated layer-2 gradient the previous iteration left (_dt2_keep) and the sign pattern its Del-1 stored
+        # (gd_del1_chain_loss_wgrad_f32): the gated [S1, 64] x [64, 128] product at the end of the step, its [S1, 128] write and
+        # the read-back are gone.  GATConv: the same with its two rank-1 terms added in front of the gate; the message gradient
+        # and the two logit gradients the previous iteration's backward left live in buffers this engine owns (_gat_bufs)
+        self._gat_bufs = self._dt2_keep = None
+        if self._chain1 and self._mode == 'gat':
             self._gat_bufs = {'dh': torch.zeros(n, self.o, **f32), 'da_src': torch.zeros(n, **f32), 'da_dst': torch.zeros(n, **f32)}
-        self._dt2_keep = torch.zeros(n, self.o, **f32) if (self._chain1 and self._gat_bufs is None) else None
-        # OPT-IN (GD_SMALL_SIDE_W1=1), measured in round 6 and NOT the default: on SMALL requests (below the row count of the fused
-        # Del-1 pass) the loss-fused W_D1 weight-gradient launch reads only what exists once Del-1 has run and nothing reads its
-        # partial sums before the tail, and at a few thousand rows neither it nor layer 2's launches fill the chip - so it can run
-        # on a side stream next to layer 2's forward, joined before the iteration overwrites dh.  synth-dblp 0.1834 -> 0.192 ms,
-        # synth-cora 0.4765 -> 0.484 ms (3 alternating pairs, profiles/r06_side_w1_ab.txt): the cross-queue dependencies of the
-        # replayed hipGraph cost more than the 17 us launch they hide - the same answer as GD_SIDE_STREAM gave at step size in round 3.
-        self._side_w1 = bool(self._tail and self._fuse_loss1 and not self._fuse_del1 and loss_type == 'both_layerwise'
-                             and self.s1 > 0 and not self._overlap and os.environ.get('GD_SMALL_SIDE_W1') == '1')
-        if self._side_w1 and self._side is None:
-            self._side = torch.cuda.Stream(device=dev)
-        # ... and the two stand-alone loss launches of a knowledge-graph step (DEC rows outside the Del rows, both layers) are one
-        self._out_pair = bool(self._out1 and self._out2 and self._fuse_loss1 and self._fuse_l2 and loss_type != 'only2_all'
-                              and _lib.lib().gd_rowtarget_mse_pair_covers(self.h, self.o) and os.environ.get('GD_NO_LOSS_PAIR') != '1')
-        self._mode = {GCNConv: 'gcn', GINConv: 'gin', GATConv: 'gat', SAGEConv: 'sage', RGCNConv: 'rgcn'}[type(conv2)]
-        self._gat_dots = os.environ.get('GD_NO_GAT_DOTS') != '1'      # attention logits from the GEMM epilogue
+        elif self._chain1:
+            self._dt2_keep = torch.zeros(n, self.o, **f32)
         self._gat_r1 = None                                            # (att_src W2, att_dst W2): constants of the frozen conv2
         if self._mode == 'gat':
             w2_ = conv2.lin_src.weight.detach()
             self._gat_r1 = ((conv2.att_src.detach().reshape(1, -1) @ w2_).reshape(-1).float().contiguous(),
                             (conv2.att_dst.detach().reshape(1, -1) @ w2_).reshape(-1).float().contiguous())
         if self._mode == 'rgcn':
+            # (cache_layer1: as for the other backbones - conv1's output is loop-invariant; _rgcn_rows_only: conv2's INPUT
+            #  GRADIENT is formed for the Del-1 rows only, the only rows that read it - see _conv2_backward_to_s1; the forward
+            #  stays whole: the DEC rows of a knowledge-graph request are the Df endpoints, most of the graph)
             from .graph import TypedNodeCSR
             self.typed = TypedNodeCSR(edge_index, edge_type.to(dev), n, conv2.num_relations)
             self.typed_s1 = None
-            if getattr(self, '_rgcn_rows_only', False) and self.s1 > 0:
+            if self._rgcn_rows_only and self.s1 > 0:
                 in1 = torch.zeros(n, dtype=torch.bool, device=dev)
                 in1[self.idx1.long()] = True
                 self.typed_s1 = self.typed.restrict_bwd(in1)
-            self.graph = None
             self._hbuf = torch.zeros(n, self.h, **f32)                # relu(z1) as the typed conv reads it
             self._dxbuf = torch.zeros(n, self.h, **f32)               # conv2's input gradient
             # tile plans and packed relation weights are made here, outside any graph capture
             for c_, din, dout, tr in ((conv1, self.x.shape[1], self.h, 0), (conv2, self.h, self.o, 0), (conv2, self.o, self.h, 1)):
-                if int(_lib.lib().gd_rgcn_tile_kl(din, dout, c_.num_blocks or 1, tr)) > 0 and os.environ.get('GD_RGCN_NODE_MAJOR') != '1':
+                if int(lib.gd_rgcn_tile_kl(din, dout, c_.num_blocks or 1, tr)) > 0 and not knobs.rgcn_node_major:
                     tg_ = self.typed_s1 if (tr and self.typed_s1 is not None) else self.typed
                     if ops.rgcn_wave_form(din, dout, c_.num_blocks or 1, n, din) and self.typed.num_relations < 65536:
                         tg_.wave_plan(bool(tr))
                     else:
                         tg_.tile_plan(bool(tr))
                     ops.rgcn_packed_weight(c_.weight.detach(), c_.num_blocks or 1, din, dout, tr)
-        else:
-            gmode = {'gcn': 'gcn', 'gin': 'sum', 'gat': 'gat', 'sage': 'mean'}[self._mode]
-            self.graph = graph_for(edge_index, n, gmode)
         if self._mode == 'sage':
             # frozen: [W_l ; W_r] of conv2 stacked once -> one GEMM gives (t2_l | t2_r), and its transpose
             # side gives dh from (dt2 | dp2)
             self._w2cat = torch.cat([conv2.lin_l.weight.detach(), conv2.lin_r.weight.detach()], 0).contiguous()
+        # Affected rows only (_rows_only; GCN, GIN, GraphSAGE; GAT: its aggregation kernels): the training graph holds the S_Df edges
+        # plus self loops, so a row outside the 2-hop set S2 neither reads nor feeds a row inside it and no loss term sees it - its
+        # transforms and aggregates influence nothing the iteration produces.  With this option every N-row kernel runs on the S2
+        # rows (the transposed aggregation on S1): identical Del weights and losses, cost proportional to the
+        # affected subgraph instead of the graph.  OFF by default (upstream computes every row and the benchmark's
+        # `value` is measured that way); the trainer turns it on.  Verified closed under the graph first (facts.closed).
+        if self._rows_only:
+            from .graph import SplitPlan
+            self._plan2 = SplitPlan(self.graph.rowptr, rows=self.idx2)
+            self._plan_t1 = SplitPlan(self.graph.rowptr_t, rows=self.idx1)
+            self._t1buf = torch.zeros(n, self.h, **f32)
+            self._t1rbuf = torch.zeros(n, self.h, **f32) if self._mode == 'sage' else None
+            self._t2buf = torch.zeros(n, self.o * (2 if self._mode == 'sage' else 1), **f32)
+            # (round 6) the rows-only step is chained as well: its transposed aggregation writes the S1 rows of the buffer the next
+            # iteration's Del-1 pass reads (all it reads)
+            self._dt2buf = self._dt2_keep if self._dt2_keep is not None else torch.zeros(n, self.o, **f32)
+            self._adots = torch.zeros(2, n, **f32)                     # GAT logits of a row subset
+            if self._split1:
+                self.pre1.zero_()
+            self.p2.zero_()
         # Optional: the frozen layer-1 output p1 = conv1(x) is loop-invariant (fixed x, edges and
         # weights), so it can be computed once.  OFF by default: upstream recomputes it every epoch and
         # the benchmark's `value` is measured that way; the trainer turns it on (identical results).
-        # Affected rows only (GCN, GIN, GraphSAGE; GAT: its aggregation kernels): the training graph holds the S_Df edges plus self loops, so a row outside the
-        # 2-hop set S2 neither reads nor feeds a row inside it and no loss term sees it - its transforms and
-        # aggregates influence nothing the iteration produces.  With this option every N-row kernel runs on the S2
-        # rows (the transposed aggregation on S1): identical Del weights and losses, cost proportional to the
-        # affected subgraph instead of the graph.  OFF by default (upstream computes every row and the benchmark's
-        # `value` is measured that way); the trainer turns it on.  Verified closed under the graph first.
-        self._rows_only = False
-        gin_ok = self._mode == 'gin' and conv1.nn.out_features <= conv1.nn.in_features and conv2.nn.out_features <= conv2.nn.in_features
-        if (affected_rows_only and (self._mode in ('gcn', 'gat', 'sage') or gin_ok) and self._split2 and self.s2 > 0
-                and not self._out1 and not self._out2):        # (loss rows outside the Del rows read conv outputs of rows outside S2)
-            g = self.graph
-            in2 = torch.zeros(n, dtype=torch.bool, device=dev)
-            in2[self.idx2.long()] = True
-            in1_rows = torch.zeros(n, dtype=torch.bool, device=dev)
-            in1_rows[self.idx1.long()] = True
-            deg = (g.rowptr[1:] - g.rowptr[:-1]).long()
-            erow = torch.repeat_interleave(torch.arange(n, device=dev), deg)
-            closed = bool(in2[g.col.long()[in2[erow]]].all()) and bool(in2[self.idx1.long()].all())
-            deg_t = (g.rowptr_t[1:] - g.rowptr_t[:-1]).long()
-            erow_t = torch.repeat_interleave(torch.arange(n, device=dev), deg_t)
-            closed = closed and bool(in2[g.col_t.long()[in1_rows[erow_t]]].all())
-            if closed:
-                from .graph import SplitPlan
-                self._plan2 = SplitPlan(g.rowptr, rows=self.idx2)
-                self._plan_t1 = SplitPlan(g.rowptr_t, rows=self.idx1)
-                self._t1buf = torch.zeros(n, self.h, **f32)
-                self._t1rbuf = torch.zeros(n, self.h, **f32) if self._mode == 'sage' else None
-                self._t2buf = torch.zeros(n, self.o * (2 if self._mode == 'sage' else 1), **f32)
-                self._dt2buf = torch.zeros(n, self.o, **f32)
-                self._adots = torch.zeros(2, n, **f32)                     # GAT logits of a row subset
-                if self._split1:
-                    self.pre1.zero_()
-                self.p2.zero_()
-                self._rows_only = True
-        if self._rows_only and self._chain1 and self._dt2_keep is not None:
-            # (round 6) the rows-only step is chained as well: its transposed aggregation writes the S1 rows of the buffer the next
-            # iteration's Del-1 pass reads (all it reads); before, `_chain1` stayed set while the step ran the unchained form
-            self._dt2buf = self._dt2_keep
         self.cache_layer1 = cache_layer1
         if cache_layer1:
             with torch.no_grad():
@@ -688,18 +761,33 @@ class NodeembEngine:
                     if self.s1:
                         self.xs1.copy_(self.p1[self.idx1.long()])
 
+    def _affected_rows_closed(self):
+        """Does no row of S2 read a row outside it, does S1 lie in S2, and does no row of S1 feed a row outside S2?"""
+        g, n, dev = self.graph, self.n, self.x.device
+        in2 = torch.zeros(n, dtype=torch.bool, device=dev)
+        in2[self.idx2.long()] = True
+        in1_rows = torch.zeros(n, dtype=torch.bool, device=dev)
+        in1_rows[self.idx1.long()] = True
+        deg = (g.rowptr[1:] - g.rowptr[:-1]).long()
+        erow = torch.repeat_interleave(torch.arange(n, device=dev), deg)
+        closed = bool(in2[g.col.long()[in2[erow]]].all()) and bool(in2[self.idx1.long()].all())
+        deg_t = (g.rowptr_t[1:] - g.rowptr_t[:-1]).long()
+        erow_t = torch.repeat_interleave(torch.arange(n, device=dev), deg_t)
+        return closed and bool(in2[g.col_t.long()[in1_rows[erow_t]]].all())
+
     # ------------------------------------------------------------------ pieces
     @staticmethod
     def _mfma_weight(weight):
         out_f, in_f = weight.shape
         return in_f % 32 == 0 and out_f % 32 == 0 and out_f <= 128 and in_f * out_f * 4 <= 64 * 1024
 
-    def _linear(self, x, weight, relu_in=False):
+    def _linear(self, x, weight, relu_in=False, idx=None, out=None):
         """x @ weight^T on the matrix-core kernels: the whole-weight-in-LDS row kernel when the weight fits its 64 KB
-        image, else the K-tiled kernel (wide bag-of-words inputs: the padded copy of x is made once)."""
+        image, else the K-tiled kernel (wide bag-of-words inputs: the padded copy of x is made once).
+        idx / out: the listed rows only, written to the same rows of out - always the row kernel (it takes any widths)."""
         out_f, in_f = weight.shape
-        if in_f % 32 == 0 and out_f % 32 == 0 and out_f <= 128 and in_f * out_f * 4 <= 64 * 1024:
-            return ops.rows_gemm(x, None, weight, trans_w=True, const_w=True, relu_in=relu_in)
+        if idx is not None or self._mfma_weight(weight):
+            return ops.rows_gemm(x, idx, weight, trans_w=True, const_w=True, relu_in=relu_in, out=out)
         if ops.mfma_out_width(out_f):
             xin = torch.relu(x) if relu_in else x
             return ops.gemm_wide(xin, ops._const_weight(weight, True)[0], const_x=not relu_in, const_w=True)
@@ -708,15 +796,22 @@ class NodeembEngine:
         raise NotImplementedError(f'NodeembEngine: a {in_f} -> {out_f} Linear has no kernel (inputs above 1,024 floats need an output '
                                   'width in {32, 64, 96, 128}); there is no vendor-BLAS fallback')
 
-    def _linear_relu_z1(self, weight):
-        """relu(z1) @ weight^T where z1 = Del-1 output on the S1 rows and conv1 output elsewhere."""
-        if not self._split1:
-            return self._linear(self.z1, weight, relu_in=True)
-        out_f, in_f = weight.shape
-        if in_f % 32 == 0 and out_f % 32 == 0 and out_f <= 128 and in_f * out_f * 4 <= 64 * 1024:
-            return ops.rows_gemm_select(self.pre1, self.z1, self._sel1, weight, trans_w=True, const_w=True, relu_in=True)
+    def _linear_relu_z1(self, weight, idx=None, out=None):
+        """relu(z1) @ weight^T where z1 = Del-1 output on the S1 rows and conv1 output elsewhere (idx / out: as _linear)."""
+        if not self._split1:       # (layer 1 cached: z1 holds conv1's output with the Del'd rows written over it)
+            return self._linear(self.z1, weight, relu_in=True, idx=idx, out=out)
+        if idx is not None or self._mfma_weight(weight):
+            return ops.rows_gemm_select(self.pre1, self.z1, self._sel1, weight, trans_w=True, const_w=True, relu_in=True,
+                                        out=out, idx=idx)
         z = torch.where(self._sel1.bool()[:, None], self.z1, self.pre1)
         return self._linear(z, weight, relu_in=True)
+
+    def _layer1_rows(self, weight):
+        """(idx, out, plan) of a layer-1 transform and its aggregation: the S2 rows into the fixed buffer under the rows-only
+        plan where the step runs on the affected rows and the row-subset GEMM has the weight's widths, else every row."""
+        if self._rows_only and self._split1 and self._mfma_weight(weight):
+            return self.idx2, self._t1buf, self._plan2
+        return None, None, None
 
     def _conv1_forward(self):
         """Frozen layer 1, recomputed every step exactly as upstream does, written into z1."""
@@ -724,49 +819,40 @@ class NodeembEngine:
         g = self.graph
         if self._mode == 'rgcn':
             self._rgcn_conv(c, self.x, self.pre1, 0)
-        elif self._mode == 'gcn' and self._rows_only and self._split1 and self._mfma_weight(c.lin.weight):
-            ops.rows_gemm(self.x, self.idx2, c.lin.weight, trans_w=True, const_w=True, out=self._t1buf)
-            self._spmm(False, g.val, self._t1buf, self.pre1, c.bias, 0.0, plan=self._plan2)
         elif self._mode == 'gcn':
-            self._spmm(False, g.val, self._linear(self.x, c.lin.weight), self.pre1, c.bias, 0.0)
-        elif self._mode == 'gin' and self._rows_only and self._split1 and self._mfma_weight(c.nn.weight):
-            lin = c.nn
-            ops.rows_gemm(self.x, self.idx2, lin.weight, trans_w=True, const_w=True, out=self._t1buf)
-            self._spmm(False, None, self._t1buf, self.pre1, lin.bias, 1.0 + c.eps, plan=self._plan2)
+            idx, out, plan = self._layer1_rows(c.lin.weight)
+            self._spmm(False, g.val, self._linear(self.x, c.lin.weight, idx=idx, out=out), self.pre1, c.bias, 0.0, plan=plan)
         elif self._mode == 'gin':
             lin = c.nn
             if lin.out_features <= lin.in_features:
-                self._spmm(False, None, self._linear(self.x, lin.weight), self.pre1, lin.bias, 1.0 + c.eps)
-            else:
+                idx, out, plan = self._layer1_rows(lin.weight)
+                self._spmm(False, None, self._linear(self.x, lin.weight, idx=idx, out=out), self.pre1, lin.bias, 1.0 + c.eps, plan=plan)
+            else:                                  # (aggregate first; the rows-only step needs gin_ok, so it never comes here)
                 agg = torch.empty_like(self.x)
                 self._spmm(False, None, self.x, agg, None, 1.0 + c.eps)
                 ops.rows_gemm(agg, None, lin.weight, trans_w=True, const_w=True, bias=lin.bias, out=self.pre1)
-        elif self._mode == 'sage' and self._rows_only and self._split1 and self._mfma_weight(c.lin_l.weight):
-            ops.rows_gemm(self.x, self.idx2, c.lin_l.weight, trans_w=True, const_w=True, out=self._t1buf)
-            ops.rows_gemm(self.x, self.idx2, c.lin_r.weight, trans_w=True, const_w=True, out=self._t1rbuf)
-            self._spmm(False, g.val, self._t1buf, self.pre1, c.lin_l.bias, 1.0, x_self=self._t1rbuf, plan=self._plan2)
         elif self._mode == 'sage':
             # out_i = mean_j (x_j W_l^T) + b_l + x_i W_r^T  (transform first, then aggregate at width H)
-            t_l = self._linear(self.x, c.lin_l.weight)
-            if (self._mfma_weight(c.lin_r.weight) and ops.rows_gemm_accumulate_ok(self.n, c.lin_r.weight.shape[1], c.lin_r.weight.shape[0])
-                    and os.environ.get('GD_SAGE_ROOT_IN_SPMM') != '1'):
+            idx, out, plan = self._layer1_rows(c.lin_l.weight)
+            t_l = self._linear(self.x, c.lin_l.weight, idx=idx, out=out)
+            if (idx is None and self._mfma_weight(c.lin_r.weight)
+                    and ops.rows_gemm_accumulate_ok(self.n, c.lin_r.weight.shape[1], c.lin_r.weight.shape[0])
+                    and not self.knobs.sage_root_in_spmm):
                 # (round 6) the root term is ADDED by its own product (gd_rows_gemm_accumulate_f32: the accumulators of a unit start
                 # from the aggregated rows) instead of travelling through the aggregation as a second row stream: the latency-bound
                 # sweep reads one row per edge less per target, the matrix-bound product has the memory to spare
                 self._spmm(False, g.val, t_l, self.pre1, c.lin_l.bias, 0.0)
                 ops.rows_gemm_accumulate_(self.pre1, self.x, None, c.lin_r.weight, trans_w=True, const_w=True)
             else:
-                t_r = self._linear(self.x, c.lin_r.weight)
-                self._spmm(False, g.val, t_l, self.pre1, c.lin_l.bias, 1.0, x_self=t_r)
+                t_r = self._linear(self.x, c.lin_r.weight, idx=idx, out=None if idx is None else self._t1rbuf)
+                self._spmm(False, g.val, t_l, self.pre1, c.lin_l.bias, 1.0, x_self=t_r, plan=plan)
         else:
             wsrc = c.lin_src.weight
-            if self._rows_only and self._split1 and self._mfma_weight(wsrc):
-                h1 = ops.rows_gemm(self.x, self.idx2, wsrc, trans_w=True, const_w=True, out=self._t1buf)       # rows outside stay 0
-                a_src, a_dst = ops.row_dots(h1, c.att_src, c.att_dst)
-            elif self._gat_dots and ops.rows_gemm_dots_ok(wsrc.shape[1], wsrc.shape[0], self.n):
+            idx, out, _ = self._layer1_rows(wsrc)                 # (rows outside stay 0)
+            if idx is None and self._gat_dots and ops.rows_gemm_dots_ok(wsrc.shape[1], wsrc.shape[0], self.n):
                 h1, a_src, a_dst = ops.rows_gemm_dots(self.x, wsrc, c.att_src, c.att_dst, const_w=True)   # logits from the epilogue
             else:
-                h1 = self._linear(self.x, wsrc)
+                h1 = self._linear(self.x, wsrc, idx=idx, out=out)
                 a_src, a_dst = ops.row_dots(h1, c.att_src, c.att_dst)
             ops.gat_forward_raw(g, h1, a_src, a_dst, c.bias, c.negative_slope, out=self.pre1,
                                 plan=self._plan2 if (self._rows_only and self._split1) else None)
@@ -788,49 +874,26 @@ class NodeembEngine:
                 torch.where(self._sel1.bool()[:, None], self.z1, self.pre1, out=self._hbuf)
                 self._hbuf.clamp_(min=0)
                 self._rgcn_conv(c, self._hbuf, self.p2, 0)
-            elif ops.rgcn_wave_relu_ok(self.typed, self.z1, self.p2, c.num_blocks or 1) and os.environ.get('GD_RGCN_RELU_PASS') != '1':
+            elif ops.rgcn_wave_relu_ok(self.typed, self.z1, self.p2, c.num_blocks or 1) and not self.knobs.rgcn_relu_pass:
                 # relu(z1) is formed where the two products read z1 (the typed conv's gathered rows, the root product's
                 # operand path): no clamp pass over [n, h], no torch op in the step
                 self._rgcn_conv(c, self.z1, self.p2, 0, relu_in=True)
             else:
                 torch.clamp(self.z1, min=0, out=self._hbuf)
                 self._rgcn_conv(c, self._hbuf, self.p2, 0)
-        elif self._mode == 'gcn' and self._rows_only:
-            if self._split1:
-                t2 = ops.rows_gemm_select(self.pre1, self.z1, self._sel1, c.lin.weight, trans_w=True, const_w=True, relu_in=True,
-                                          out=self._t2buf, idx=self.idx2)
-            else:       # layer 1 cached: z1 holds conv1's output with the Del'd rows written over it
-                t2 = ops.rows_gemm(self.z1, self.idx2, c.lin.weight, trans_w=True, const_w=True, relu_in=True, out=self._t2buf)
-            self._spmm(False, self.graph.val, t2, self.p2, c.bias, 0.0, plan=self._plan2)
-        elif self._mode == 'gcn':
-            t2 = self._linear_relu_z1(c.lin.weight)
-            self._spmm(False, self.graph.val, t2, self.p2, c.bias, 0.0)
-        elif self._mode == 'gin' and self._rows_only:
-            lin = c.nn
-            if self._split1:
-                t2 = ops.rows_gemm_select(self.pre1, self.z1, self._sel1, lin.weight, trans_w=True, const_w=True, relu_in=True,
-                                          out=self._t2buf, idx=self.idx2)
+        elif self._mode in ('gcn', 'gin', 'sage'):
+            # relu(z1) @ W2^T, then the aggregation: on the S2 rows into the fixed buffer under the rows-only plan, or on every row
+            idx, out, plan = (self.idx2, self._t2buf, self._plan2) if self._rows_only else (None, None, None)
+            if self._mode == 'gcn':
+                self._spmm(False, self.graph.val, self._linear_relu_z1(c.lin.weight, idx, out), self.p2, c.bias, 0.0, plan=plan)
+            elif self._mode == 'gin':
+                lin = c.nn
+                if lin.out_features > lin.in_features:
+                    raise NotImplementedError('GIN layer that widens its input is not on the fused path')
+                self._spmm(False, None, self._linear_relu_z1(lin.weight, idx, out), self.p2, lin.bias, 1.0 + c.eps, plan=plan)
             else:
-                t2 = ops.rows_gemm(self.z1, self.idx2, lin.weight, trans_w=True, const_w=True, relu_in=True, out=self._t2buf)
-            self._spmm(False, None, t2, self.p2, lin.bias, 1.0 + c.eps, plan=self._plan2)
-        elif self._mode == 'gin':
-            lin = c.nn
-            if lin.out_features <= lin.in_features:
-                t2 = self._linear_relu_z1(lin.weight)
-                self._spmm(False, None, t2, self.p2, lin.bias, 1.0 + c.eps)
-            else:
-                raise NotImplementedError('GIN layer that widens its input is not on the fused path')
-        elif self._mode == 'sage' and self._rows_only:
-            if self._split1:
-                t2 = ops.rows_gemm_select(self.pre1, self.z1, self._sel1, self._w2cat, trans_w=True, const_w=True, relu_in=True,
-                                          out=self._t2buf, idx=self.idx2)
-            else:
-                t2 = ops.rows_gemm(self.z1, self.idx2, self._w2cat, trans_w=True, const_w=True, relu_in=True, out=self._t2buf)
-            self._spmm(False, self.graph.val, t2[:, :self.o], self.p2, c.lin_l.bias, 1.0, x_self=t2[:, self.o:],
-                       plan=self._plan2)
-        elif self._mode == 'sage':
-            t2 = self._linear_relu_z1(self._w2cat)              # [N, 2*O] = (t2_l | t2_r)
-            self._spmm(False, self.graph.val, t2[:, :self.o], self.p2, c.lin_l.bias, 1.0, x_self=t2[:, self.o:])
+                t2 = self._linear_relu_z1(self._w2cat, idx, out)              # [N, 2*O] = (t2_l | t2_r)
+                self._spmm(False, self.graph.val, t2[:, :self.o], self.p2, c.lin_l.bias, 1.0, x_self=t2[:, self.o:], plan=plan)
         else:   # gat
             wsrc = c.lin_src.weight
             if self._gat_dots and self._split1 and ops.rows_gemm_dots_ok(wsrc.shape[1], wsrc.shape[0], self.s2 if self._rows_only else self.n,
@@ -870,20 +933,15 @@ class NodeembEngine:
             dt2, w2 = self.dcat, self._w2cat
         elif self._mode in ('gcn', 'gin'):
             chain = self._chain1
-            dt2 = self._dt2_keep if chain else torch.empty(self.n, self.o, dtype=torch.float32, device=self.x.device)
-            if self._mode == 'gcn' and self._rows_only:
-                dt2 = self._dt2buf
-                self._spmm(True, g.val_t, self.dz2, dt2, None, 0.0, plan=self._plan_t1)
-                w2 = c.lin.weight
-            elif self._mode == 'gcn':
-                self._spmm(True, g.val_t, self.dz2, dt2, None, 0.0)
-                w2 = c.lin.weight
-            elif self._rows_only:
-                dt2 = self._dt2buf
-                self._spmm(True, None, self.dz2, dt2, None, 1.0 + c.eps, plan=self._plan_t1)
-                w2 = c.nn.weight
+            if self._rows_only:           # (the S1 rows of a fixed buffer: the chained form's own where the step is chained)
+                dt2, plan = self._dt2buf, self._plan_t1
             else:
-                self._spmm(True, None, self.dz2, dt2, None, 1.0 + c.eps)
+                dt2, plan = (self._dt2_keep if chain else torch.empty(self.n, self.o, dtype=torch.float32, device=self.x.device)), None
+            if self._mode == 'gcn':
+                self._spmm(True, g.val_t, self.dz2, dt2, None, 0.0, plan=plan)
+                w2 = c.lin.weight
+            else:
+                self._spmm(True, None, self.dz2, dt2, None, 1.0 + c.eps, plan=plan)
                 w2 = c.nn.weight
             if chain:
                 return                    # (the NEXT iteration's Del-1 pass forms dh[S1] = (dt2[S1] W2) * [z1[S1] > 0] itself)
@@ -897,7 +955,7 @@ class NodeembEngine:
             if chain:
                 return            # (the NEXT iteration's Del-1 pass forms dh[S1] from dt2, da_src, da_dst and the stored sign pattern)
             w2 = c.lin_src.weight
-            if self._mfma_weight(w2) and os.environ.get('GD_NO_GAT_RANK1_EPILOGUE') != '1':
+            if self._mfma_weight(w2) and not self.knobs.no_gat_rank1_epilogue:
                 # dh2 = A_alpha^T dy + da_src (x) att_src + da_dst (x) att_dst only feeds the product below: the two
                 # rank-1 terms are added on ITS output side, (a (x) u) W2 = a (x) (u W2), with u W2 constants of the
                 # frozen backbone - the pass over dh2 (gd_rank1_add2_f32) disappears
@@ -920,47 +978,23 @@ class NodeembEngine:
         """out (+)= a^T (g + g_add) over the selected rows; with `adam` the optimizer update of that Del
         weight is applied inside the split-K reduction (one launch less)."""
         d_a, d_b = a_compact.shape[1], g.shape[1]
-        if adam is not None and self._tail:
-            # partial products only: the reduction, the Adam update and the loss finalize are one launch at the end of the step
-            adam.applied += 1
-            self._tail_acc[0 if adam is self.adam1 else 1] = int(accumulate)
-            check(_lib.lib().gd_rows_gemm_wgrad_f32(ptr(a_compact), a_compact.stride(0), ptr(a_idx), ptr(g), g.stride(0),
-                                                    ptr(g_idx), None, ptr(g_add), n_sel, d_a, d_b, None,
-                                                    int(accumulate), ptr(ws), stream_ptr(g.device)),
-                  'gd_rows_gemm_wgrad_f32')
-            return
-        if adam is not None and self._overlap:
-            adam.applied += 1
-            check(_lib.lib().gd_rows_gemm_wgrad_f32(ptr(a_compact), a_compact.stride(0), ptr(a_idx), ptr(g), g.stride(0),
-                                                    ptr(g_idx), None, ptr(g_add), n_sel, d_a, d_b, None,
-                                                    int(accumulate), ptr(ws), stream_ptr(g.device)),
-                  'gd_rows_gemm_wgrad_f32')
-            self._reduce_on_side(ws, n_sel, d_a, d_b, out, accumulate, adam)
-            return
         if adam is not None:
             adam.applied += 1
-            check(_lib.lib().gd_rows_gemm_wgrad_adam_f32(
-                ptr(a_compact), a_compact.stride(0), ptr(a_idx), ptr(g), g.stride(0), ptr(g_idx), None, ptr(g_add), n_sel,
-                d_a, d_b, ptr(out), int(accumulate), ptr(ws), ptr(adam.param), ptr(adam.m), ptr(adam.v),
-                ptr(adam.iter_ctr), adam.lr, adam.betas[0], adam.betas[1], adam.eps, stream_ptr(g.device)),
-                'gd_rows_gemm_wgrad_adam_f32')
+        if adam is None or self._tail:
+            # under the tail launch partial products only (no `out`): the reduction, the Adam update and the loss finalize are
+            # one launch at the end of the step
+            if adam is not None:
+                self._tail_acc[0 if adam is self.adam1 else 1] = int(accumulate)
+            check(_lib.lib().gd_rows_gemm_wgrad_f32(ptr(a_compact), a_compact.stride(0), ptr(a_idx), ptr(g), g.stride(0),
+                                                    ptr(g_idx), None, ptr(g_add), n_sel, d_a, d_b, ptr(out) if adam is None else None,
+                                                    int(accumulate), ptr(ws), stream_ptr(g.device)),
+                  'gd_rows_gemm_wgrad_f32')
             return
-        check(_lib.lib().gd_rows_gemm_wgrad_f32(ptr(a_compact), a_compact.stride(0), ptr(a_idx), ptr(g), g.stride(0),
-                                                ptr(g_idx), None, ptr(g_add), n_sel, d_a, d_b, ptr(out),
-                                                int(accumulate), ptr(ws), stream_ptr(g.device)),
-              'gd_rows_gemm_wgrad_f32')
-
-    def _fork(self):
-        """Context: launches inside go to the side stream, ordered after everything enqueued on the current one."""
-        self._side.wait_stream(torch.cuda.current_stream())
-        return torch.cuda.stream(self._side)
-
-    def _reduce_on_side(self, ws, n_sel, d_a, d_b, out, accumulate, adam):
-        with self._fork():
-            check(_lib.lib().gd_rows_gemm_wgrad_reduce_f32(
-                ptr(ws), n_sel, d_a, d_b, ptr(out), int(accumulate), ptr(adam.param), ptr(adam.m), ptr(adam.v),
-                ptr(adam.iter_ctr), adam.lr, adam.betas[0], adam.betas[1], adam.eps, stream_ptr(out.device)),
-                'gd_rows_gemm_wgrad_reduce_f32')
+        check(_lib.lib().gd_rows_gemm_wgrad_adam_f32(
+            ptr(a_compact), a_compact.stride(0), ptr(a_idx), ptr(g), g.stride(0), ptr(g_idx), None, ptr(g_add), n_sel,
+            d_a, d_b, ptr(out), int(accumulate), ptr(ws), ptr(adam.param), ptr(adam.m), ptr(adam.v),
+            ptr(adam.iter_ctr), adam.lr, adam.betas[0], adam.betas[1], adam.eps, stream_ptr(g.device)),
+            'gd_rows_gemm_wgrad_adam_f32')
 
     # ------------------------------------------------------------------ one iteration
     def _wgrad1(self, accumulate, g_add):
@@ -974,22 +1008,20 @@ class NodeembEngine:
             return
         a = self.adam1
         a.applied += 1
-        ov = self._overlap or self._tail
         if self._tail:
             self._tail_acc[0] = int(accumulate)
         check(_lib.lib().gd_rows_gemm_wgrad_loss_f32(
             ptr(a1), a1.stride(0), ptr(a1_idx), ptr(self.z1), self.z1.stride(0), ptr(self.idx1),
             ptr(self._slot1), ptr(self.t1.tm), ptr(self.t1.coef), ptr(self._cnt_signed1), ptr(g_add), self.s1, self.h,
-            self.h, None if ov else ptr(self.g1), int(accumulate), ptr(self.ws1), ptr(self._lp1),
-            None if ov else ptr(a.param), ptr(a.m), ptr(a.v),
+            self.h, None if self._tail else ptr(self.g1), int(accumulate), ptr(self.ws1), ptr(self._lp1),
+            None if self._tail else ptr(a.param), ptr(a.m), ptr(a.v),
             ptr(a.iter_ctr), a.lr, a.betas[0], a.betas[1], a.eps, stream_ptr(self.x.device)),
             'gd_rows_gemm_wgrad_loss_f32')
-        if self._overlap:
-            self._reduce_on_side(self.ws1, self.s1, self.h, self.h, self.g1, accumulate, a)
 
     def _iteration(self):
         """One training iteration, a single dependent chain of launches (every kernel here fills the chip on
-        its own: running the layer-1 loss branch on a second stream measured within 1 % of this).
+        its own: running the layer-1 loss branch on a second stream measured within 1 % of this, and the two side-stream
+        forms that were tried lost - DESIGN.md section 4).
 
         W_D1 receives gradient from the layer-1 loss (dz1 rows) and, through conv2, from the layer-2
         loss (dh rows, already ReLU-gated).  Both are products with the same loop-invariant operand
@@ -1024,9 +1056,6 @@ class NodeembEngine:
                 self.t1.launch_outside(self.z1, None, self._lp1[2 * self._lp1_blocks:])
             if self._fuse_del1:
                 pass                                             # (its weight-gradient partials came out of the Del-1 pass)
-            elif lt == 'both_layerwise' and self._side_w1:
-                with self._fork():
-                    self._wgrad1(False, self.dh)
             elif lt == 'both_layerwise':
                 self._wgrad1(False, self.dh)
             elif lt == 'only1':
@@ -1047,39 +1076,24 @@ class NodeembEngine:
                 ops.rows_gemm(self.p2, self.idx2, self.wd2, out=self.z2, save_in=self.xs2)
                 self.t2.launch(self.z2, self.dz2, s2)
             # ---- backward + update
-            if self._side_w1:                                    # (join: the backward below overwrites dh, the tail reads the partials)
-                torch.cuda.current_stream().wait_stream(self._side)
             if lt == 'both_layerwise':
                 self._layer2_backward()                          # leaves dh for the next iteration
-                if not self._fuse_l2 and not self._tail:
-                    self.adam2.apply(self.g2)
             elif lt == 'both_all':
                 self._layer2_backward(g2_accumulate=True)
                 self._wgrad1(True, self.dh)
-                if not self._fuse_l2 and not self._tail:
-                    self.adam2.apply(self.g2)
             elif lt == 'only2_layerwise':
                 self._layer2_backward(to_w1=False)
-                if not self._fuse_l2 and not self._tail:
-                    self.adam2.apply(self.g2)
             elif lt == 'only2_all':
                 self._layer2_backward()
                 a1, a1_idx = (self.pre1, self.idx1) if self._split1 else (self.xs1, None)
                 self._wgrad(a1, self.dh, self.idx1, self.s1, self.g1, False, self.ws1, adam=self.adam1, a_idx=a1_idx)
-                if not self._fuse_l2 and not self._tail:
-                    self.adam2.apply(self.g2)
+            if lt != 'only1' and not self._fuse_l2 and not self._tail:      # (else W_D2's step rode on a launch above or waits in the tail)
+                self.adam2.apply(self.g2)
             # ---- loss sums -> history ring, advance the iteration counter (Adam's step number)
             p1, n1 = ((self._lp1, self._lp1_blocks + (self.t1.outside_blocks() if self._out1 else 0)) if self._fuse_loss1
                       else (self.t1.partials, self.t1.n_partial_blocks()))
             p2, n2 = ((self._lp2, self._lp2_blocks + (self.t2.outside_blocks() if self._out2 else 0)) if self._fuse_l2
                       else (self.t2.partials, self.t2.n_partial_blocks()))
-
-            def finalize():
-                check(_lib.lib().gd_loss_finalize_f32(
-                    ptr(p1) if fused_fin else None, n1 if fused_fin else 0,
-                    ptr(p2) if fused_fin else None, n2 if fused_fin else 0,
-                    None if fused_fin else ptr(self.sums), ptr(self.hist), self.hist.shape[0], ptr(self.hist_pos),
-                    ptr(self.iter_ctr), stream_ptr(self.x.device)), 'gd_loss_finalize_f32')
             if self._tail:
                 a1, a2 = self.adam1, self.adam2
                 lib_ = _lib.lib()
@@ -1091,12 +1105,12 @@ class NodeembEngine:
                     ptr(a2.m), ptr(a2.v), a1.lr, a1.betas[0], a1.betas[1], a1.eps, ptr(p1), n1, ptr(p2), n2, ptr(self.hist),
                     self.hist.shape[0], ptr(self.hist_pos), ptr(self.iter_ctr), ptr(self._arrive), stream_ptr(self.x.device)),
                     'gd_step_tail_parts_f32')
-            elif self._overlap:
-                with self._fork():
-                    finalize()
-                torch.cuda.current_stream().wait_stream(self._side)       # join: the iteration ends when both branches have
             else:
-                finalize()
+                check(_lib.lib().gd_loss_finalize_f32(
+                    ptr(p1) if fused_fin else None, n1 if fused_fin else 0,
+                    ptr(p2) if fused_fin else None, n2 if fused_fin else 0,
+                    None if fused_fin else ptr(self.sums), ptr(self.hist), self.hist.shape[0], ptr(self.hist_pos),
+                    ptr(self.iter_ctr), stream_ptr(self.x.device)), 'gd_loss_finalize_f32')
             if self._user_wd2 is not None:          # padded class dimension: the caller's W_D2 is the top-left block
                 self._user_wd2.data.copy_(self.wd2.data[:self._o_true, :self._o_true])
 
@@ -1198,47 +1212,23 @@ class NodeembEngine:
             return
         if self._graph is None:
             self._capture()                               # warms the libraries up on scratch state first
-        if getattr(self, '_graph_k', None) is None or self._graph_k[0] != unroll:
-            saved = [t.clone() for t in self._mutable_state()]
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                for _ in range(unroll):
-                    self._iteration()
-            # the first launch of a graph exec uploads it to the device (tens of us): do it now, on state that is
-            # restored right after - a short run (the driver times 20 steps = 5 launches) should not pay it
-            graph.replay()
-            torch.cuda.synchronize()
-            for t, sv in zip(self._mutable_state(), saved):
-                t.copy_(sv)
-            self._graph_k = (unroll, graph)
+        if self._graph_k is None or self._graph_k[0] != unroll:
+            self._graph_k = (unroll, capture_iterations(self._iteration, self._mutable_state, unroll, warm_up=False))
 
     def _mutable_state(self):
         state = [self.wd1.data, self.wd2.data, self.g1, self.g2, self.adam1.m, self.adam1.v, self.iter_ctr,
                  self.adam2.m, self.adam2.v, self.hist, self.hist_pos, self.dz1, self.dz2, self.dh]
-        if getattr(self, '_chain1', False):                 # carried from one iteration to the next in the chained form
+        if self._chain1:                                    # carried from one iteration to the next in the chained form
             state += [self.z1_pos] + ([self._dt2_keep] if self._dt2_keep is not None else
                                       [self._gat_bufs[k] for k in ('dh', 'da_src', 'da_dst')])
-        if getattr(self, '_arrive', None) is not None:      # step_tail's check-in counter: a launch that did not finish must not
-            state.append(self._arrive)                       # leave it non-zero for the replays (ADVICE r3)
-        if getattr(self, '_user_wd2', None) is not None:    # the caller's W_D2 behind a padded class dimension
+        state.append(self._arrive)      # step_tail's check-in counter: a launch that did not finish must not leave it non-zero
+        if self._user_wd2 is not None:                      # the caller's W_D2 behind a padded class dimension
             state.append(self._user_wd2.data)
         return state
 
     def _capture(self):
-        saved = [t.clone() for t in self._mutable_state()]
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._iteration()                      # warm-up (allocator, rocBLAS handles, code objects)
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self._iteration()
-        graph.replay()                             # first launch = upload of the exec; on scratch state
-        torch.cuda.synchronize()
-        for t, s in zip(self._mutable_state(), saved):
-            t.copy_(s)                             # undo the warm-up iterations
-        self._graph = graph
+        # two eager warm-up iterations would change the trajectory: they run on a scratch copy of the mutable state
+        self._graph = capture_iterations(self._iteration, self._mutable_state)
 
     def loss_history(self):
         """[steps, 3] host tensor: train_loss, loss_r, loss_l as the reference logs them."""
