@@ -69,8 +69,43 @@ class Trainer:
         # Cora / PubMed / DBLP / CS full batch; the reference's mini-batch branch (ogbl-*, Physics) exists to fit a
         # 16-32 GB GPU - one MI355X holds these graphs whole, so it is taken only on request (--minibatch)
         if is_large(self.args.dataset) and getattr(args, 'minibatch', False):
+            self._fused_backbone_applies(model, optimizer, args)        # (--fused_backbone: leaves its reason in the log)
             return self.train_minibatch(model, data, optimizer, args)
         return self.train_fullbatch(model, data, optimizer, args)
+
+    # ------------------------------------------------------------------ --fused_backbone (gnndelete_amd/backbone.py)
+    def _fused_backbone_applies(self, model, optimizer, args):
+        """Does this run take the fused backbone step?  With the flag, trainer_log['backbone_step'] says 'fused' or why not."""
+        if not getattr(args, 'fused_backbone', False):
+            return False
+        from ...backbone import fused_backbone_unsupported
+        reason = fused_backbone_unsupported(model, args, optimizer)
+        self.trainer_log['backbone_step'] = 'fused' if reason is None else reason
+        if reason is not None:
+            print(f'--fused_backbone: {reason}; running the autograd loop', flush=True)
+        return reason is None
+
+    def _backbone_engine(self, model, data, edges, n_neg, optimizer, args):
+        """The engine of one train call: message passing and positives on `edges`, Adam's hyper-parameters and state from the
+        caller's optimizer (a second train call on the same model and optimizer continues the first)."""
+        from ...backbone import BackboneEngine
+        from .gnndelete_nodeemb import _adam_hyper
+        lr, betas, eps = _adam_hyper(optimizer)
+        engine = BackboneEngine(model, data.x, edges, edges, n_neg, lr, betas, eps, history=max(16, args.epochs))
+        engine.import_adam_state(optimizer)
+        self._backbone = engine
+        return engine
+
+    @staticmethod
+    def _cached_negative_draw(sampler, edges, num_nodes):
+        """The epoch's draw for the fused step: the same random stream as `sampler` (a trainer module's negative_sampling),
+        without its torch.unique over every positive edge on every epoch; None when the module-level name has been replaced
+        (the tests' seam), and the caller keeps calling it."""
+        from .. import graph_utils
+        if sampler is not graph_utils.negative_sampling:
+            return None
+        pos_keys = graph_utils.positive_edge_keys(edges, num_nodes)
+        return lambda n_neg: graph_utils.negative_sampling_cached(pos_keys, num_nodes, n_neg)
 
     def train_minibatch(self, model, data, optimizer, args):
         """base.py:144-227: per GraphSAINT batch, BCE link prediction on the batch's edges against one negative per
@@ -124,24 +159,39 @@ class Trainer:
         data = data.to(device)
         edges = data.train_pos_edge_index
         n_neg = int(data.dtrain_mask.sum()) if hasattr(data, 'dtrain_mask') else edges.shape[1]
+        fused = self._fused_backbone_applies(model, optimizer, args)
+        engine = None
+        draw = self._cached_negative_draw(negative_sampling, edges, data.num_nodes) if fused else None
         for epoch in range(args.epochs):
             model.train()
-            neg = negative_sampling(edges, data.num_nodes, n_neg)
-            z = model(data.x, edges)
-            logits = model.decode(z, edges, neg)
-            loss = F.binary_cross_entropy_with_logits(logits, get_link_labels(edges, neg))
-            loss.backward()
-            optimizer.step()
-            optimizer.zero_grad()
+            neg = draw(n_neg) if draw is not None else negative_sampling(edges, data.num_nodes, n_neg)
+            if fused:
+                if engine is None:                  # (sized by the first draw: the loop takes whatever count the sampler gives)
+                    engine = self._backbone_engine(model, data, edges.contiguous(), int(neg.shape[1]), optimizer, args)
+                engine.step(neg)
+            else:
+                z = model(data.x, edges)
+                logits = model.decode(z, edges, neg)
+                loss = F.binary_cross_entropy_with_logits(logits, get_link_labels(edges, neg))
+                loss.backward()
+                optimizer.step()
+                optimizer.zero_grad()
             if (epoch + 1) % args.valid_freq == 0:
+                if fused:
+                    train_loss, z = engine.last_loss(), engine.z.clone()    # the block's host read; z of this epoch's forward
+                    engine.export_adam_state(optimizer)                     # (a checkpoint below carries the optimizer's state)
+                else:
+                    train_loss = loss.item()
                 valid_loss, *_, valid_log = self.eval(model, data, 'val')
-                self._record({'epoch': epoch, 'train_loss': loss.item()}, valid_log)
+                self._record({'epoch': epoch, 'train_loss': train_loss}, valid_log)
                 if valid_loss < best_valid_loss:
                     best_valid_loss, best_epoch = valid_loss, epoch
                     print(f'Save best checkpoint at epoch {epoch:04d}. Valid loss = {valid_loss:.4f}')
                     torch.save({'model_state': model.state_dict(), 'optimizer_state': optimizer.state_dict()},
                                os.path.join(args.checkpoint_dir, 'model_best.pt'))
                     torch.save(z.detach(), os.path.join(args.checkpoint_dir, 'node_embeddings.pt'))
+        if engine is not None:
+            engine.export_adam_state(optimizer)
         self.trainer_log['training_time'] = time.time() - start
         self.trainer_log['best_epoch'] = best_epoch
         self.trainer_log['best_valid_loss'] = best_valid_loss

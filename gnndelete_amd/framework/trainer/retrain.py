@@ -35,18 +35,40 @@ class RetrainTrainer(Trainer):
         best_metric, best_epoch = 0, 0
         start = time.time()
         self.trainer_log['steps'] = []
+        fused = self._fused_backbone_applies(model, optimizer, args)
+        engine = None
+        draw = self._cached_negative_draw(negative_sampling, edges, data.num_nodes) if fused else None
+
+        def read_steps():
+            # the epochs since the last read, from the engine's loss ring: one host read per validation block, not per epoch
+            steps, hist = self.trainer_log['steps'], engine.loss_history().tolist()
+            for ep in range(len(steps), engine.steps_done):
+                steps.append({'Epoch': ep, 'train_loss': hist[ep - engine.steps_done]})
+                wandb_log(steps[-1])
+            return steps[-1]
         for epoch in range(args.epochs):
             model.train()
-            neg = negative_sampling(edge_index=edges, num_nodes=data.num_nodes, num_neg_samples=n_neg)
-            z = model(data.x, edges)
-            logits = model.decode(z, edges, neg)
-            loss = F.binary_cross_entropy_with_logits(logits, get_link_labels(edges, neg))
-            loss.backward()
-            optimizer.step()
-            optimizer.zero_grad()
-            step_log = {'Epoch': epoch, 'train_loss': loss.item()}
-            wandb_log(step_log)
-            self.trainer_log['steps'].append(step_log)
+            if draw is not None:
+                neg = draw(n_neg)
+            else:
+                neg = negative_sampling(edge_index=edges, num_nodes=data.num_nodes, num_neg_samples=n_neg)
+            if fused:
+                if engine is None:                  # (sized by the first draw: the loop takes whatever count the sampler gives)
+                    engine = self._backbone_engine(model, data, edges, int(neg.shape[1]), optimizer, args)
+                engine.step(neg)
+                if (epoch + 1) % self.args.valid_freq == 0:
+                    step_log = read_steps()
+                    engine.export_adam_state(optimizer)         # (a checkpoint below carries the optimizer's state)
+            else:
+                z = model(data.x, edges)
+                logits = model.decode(z, edges, neg)
+                loss = F.binary_cross_entropy_with_logits(logits, get_link_labels(edges, neg))
+                loss.backward()
+                optimizer.step()
+                optimizer.zero_grad()
+                step_log = {'Epoch': epoch, 'train_loss': loss.item()}
+                wandb_log(step_log)
+                self.trainer_log['steps'].append(step_log)
             if (epoch + 1) % self.args.valid_freq == 0:
                 valid_loss, dt_auc, dt_aup, df_auc, df_aup, df_logit, _, valid_log = self.eval(model, data, 'val')
                 valid_log['epoch'] = epoch
@@ -56,6 +78,9 @@ class RetrainTrainer(Trainer):
                     print(f'Save best checkpoint at epoch {epoch:04d}. Valid loss = {valid_loss:.4f}')
                     torch.save({'model_state': model.state_dict(), 'optimizer_state': optimizer.state_dict()},
                                os.path.join(args.checkpoint_dir, 'model_best.pt'))
+        if engine is not None:
+            read_steps()
+            engine.export_adam_state(optimizer)
         self.trainer_log['training_time'] = time.time() - start
         torch.save({'model_state': model.state_dict(), 'optimizer_state': optimizer.state_dict()},
                    os.path.join(args.checkpoint_dir, 'model_final.pt'))

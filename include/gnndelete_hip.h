@@ -46,7 +46,8 @@ extern "C" {
                                 gd_induced_subgraph, gd_batch_csr, gd_batch_loss_terms (+ their _workspace queries): the GraphSAINT batch step;
                                 gd_edgeprob_dec_f32, gd_edge_incidence (+ their _workspace queries), gd_rows_add_f32, gd_edgeprob_record_f32:
                                 the fused edge-probability step (entries added, none changed: the version stays);
-                                gd_rowfold_loss_f32 (+ _blocks), gd_rowfold_kld_scale_f32: the folded KLD / cosine row losses (entries added: the version stays) */
+                                gd_rowfold_loss_f32 (+ _blocks), gd_rowfold_kld_scale_f32: the folded KLD / cosine row losses (entries added: the version stays);
+                                gd_edge_bce_f32, gd_col_sum_f32 (+ their _workspace queries): the fused backbone step (entries added: the version stays) */
 
 enum {
   GD_OK = 0,
@@ -732,6 +733,41 @@ int gd_rows_add_f32(float* dz, int64_t ld_dz, int64_t n_rows, const int32_t* nod
  * hist: [capacity, 3] floats.  One thread; graph-capturable. */
 int gd_edgeprob_record_f32(const float* loss_r, const float* loss_l, float coef_r, float coef_l, float* hist,
                            int32_t capacity, int32_t* pos, void* stream);
+
+/* ---------------------------------------------------------------- fused backbone step (csrc/linkpred.hip) ---- */
+
+/* Link-prediction loss of Trainer.train_fullbatch and RetrainTrainer.train_fullbatch (framework/trainer/base.py:75-142,
+ * retrain.py:57-131), F.binary_cross_entropy_with_logits(decode(z, pos, neg), labels), value and logit gradients over the
+ * M = n_pos + n_neg decoded edges in the decoder's [pos | neg] order:
+ *     l_k = <z[a_k], z[b_k]>,   y_k = 1 for k < n_pos, else 0
+ *     loss[0] = (1/M) sum_k ( max(l_k, 0) - l_k y_k + log1p(exp(-|l_k|)) )     (finite at every finite logit)
+ *     w[k] = coef * (sigmoid(l_k) - y_k) / M                                   (formed as -sigmoid(-l) for y = 1: no 1 - 1)
+ * pos: int64 [2, n_pos] with row pitch ld_pos (elements), neg likewise; either count may be 0 (its pointer may then be NULL),
+ * M == 0 is GD_E_DIM.  An edge with an endpoint outside [0, n_nodes) reads nothing outside z and counts as a ZERO LOGIT: it
+ * adds log 2 to the sum and gets w = coef * (0.5 - y) / M; gd_edge_incidence gives such an edge no entries, so that gradient
+ * reaches no row.  With src_edge / inc_ptr / w_inc (all three or none; from gd_edge_incidence over the M edges [pos | neg] and
+ * n_nodes) the finishing launch also writes w_inc[i] = w[src_edge[i]] for every incidence i < inc_ptr[n_nodes] - the order
+ * gd_edge_dot_bwd_f32 reads.  One lane group per edge, float4 per lane; at most 2,048 blocks, which walk the edges
+ * grid-strided; one partial per block, added in block order by one thread (no float atomics): the same bits every call.
+ * workspace: gd_edge_bce_workspace(M, d) floats.  d % 4 == 0, 16-byte aligned rows of z (GD_E_DIM / GD_E_ALIGN otherwise).
+ * Two launches.  Replaces the decoder's output, torch.cat of the labels, the loss and its autograd backward. */
+int64_t gd_edge_bce_workspace(int64_t m_all, int32_t d);
+int gd_edge_bce_f32(const float* z, int64_t ld_z, int64_t n_nodes, int32_t d, const int64_t* pos, int64_t ld_pos, int64_t n_pos,
+                    const int64_t* neg, int64_t ld_neg, int64_t n_neg, float coef, float* w, float* loss,
+                    const int32_t* src_edge, const int64_t* inc_ptr, float* w_inc, float* workspace, void* stream);
+
+/* out[j] = sum_r row_w[r] * [gate[r, j] > 0] * x[r, j],  j < d, over a pitched [n_rows, d] matrix (ld elements per row).
+ * row_w NULL: weight 1.  gate NULL: no gate; else a matrix of the SAME pitch, the ReLU gate convention of
+ * gd_rows_gemm_wgrad_f32's relu_mask (an exact zero is closed); gated (optional, with a gate only; same pitch; may be x
+ * itself): receives [gate[r, j] > 0] * x[r, j], the backward through F.relu, in the same pass.  The bias gradients dy.sum(0) of the convs' backward
+ * (torch_geometric's GCNConv / GATConv as framework/models/gcn.py:11-12 and gat.py:11-12 build them), the gated form
+ * colsum(dh * [p1 > 0]), and GATConv's attention-vector gradients d att_src = sum_r da_src[r] h[r, :] (row_w = da_src).
+ * Two levels: blocks own row ranges and write one partial row each, one finishing block adds the partial rows in block order;
+ * no atomics, the same bits every call.  d % 4 == 0, d <= 1024, 16-byte aligned rows (GD_E_DIM / GD_E_ALIGN otherwise);
+ * n_rows == 0 gives zeros.  workspace: gd_col_sum_workspace(n_rows, d) floats, 16-byte aligned.  Two launches. */
+int64_t gd_col_sum_workspace(int64_t n_rows, int32_t d);
+int gd_col_sum_f32(const float* x, int64_t ld, int64_t n_rows, int32_t d, const float* row_w, const float* gate, float* gated,
+                   float* out, float* workspace, void* stream);
 
 /* ---------------------------------------------------------------- optimizer ------------ */
 
