@@ -93,7 +93,8 @@ def free_port():
 
 
 def oracle_runner(gnn, data, state, neg, ni1, ni2, dtype, device, loss_type='both_layerwise', alpha=0.5, lr=1e-3, perm=None,
-                  hidden=128, out=64, edges=None, edge_type=None, pos=None, num_edge_type=None, del_masks=None, train_mask=None):
+                  hidden=128, out=64, edges=None, edge_type=None, pos=None, num_edge_type=None, del_masks=None, train_mask=None,
+                  loss_fct='mse_mean'):
     """The oracle (oracle/gnndelete_ref.py) as plain torch ops in `dtype` on `device`, one Del-training request:
     -> (step(), snapshot(), (z1_ori, z2_ori)).  perm = a seed: the edge lists are permuted first - a different summation order
     in every scatter, i.e. ANOTHER correct implementation of the same arithmetic (the members of an fp32 ensemble).
@@ -104,7 +105,7 @@ def oracle_runner(gnn, data, state, neg, ni1, ni2, dtype, device, loss_type='bot
     the knowledge-graph request trains on data.edge_index with data.edge_type and decodes data.kg_dec_edge
     (gnndelete_nodeemb.py:745-800; del_masks = the masks its Del operators were built with, train_mask = data.dr_mask: that
     trainer's forward runs on the retained edges, not on S_Df), the node-deletion request on
-    the undirected data.edge_index (:498-657)."""
+    the undirected data.edge_index (:498-657).  loss_fct: a key of the oracle's LOSSES (the KLD / cosine families)."""
     from oracle import gnndelete_ref as R
     # (the GPU box has 256 host threads: the oracle's small host-side tensor ops are ~6 x slower with all of them than with 32)
     torch.set_num_threads(min(32, torch.get_num_threads()))
@@ -138,7 +139,7 @@ def oracle_runner(gnn, data, state, neg, ni1, ni2, dtype, device, loss_type='bot
               ni_mask2=ni2.to(device))
     opt = R.make_optimizer(ref, loss_type, lr)
     def step():
-        log = R.nodeemb_epoch(ref, lambda: ref(x, es, t_sdf, return_all_emb=True), tg, opt, loss_type, alpha, R.LOSSES['mse_mean'])
+        log = R.nodeemb_epoch(ref, lambda: ref(x, es, t_sdf, return_all_emb=True), tg, opt, loss_type, alpha, R.LOSSES[loss_fct])
         return {k: log[k] for k in ('train_loss', 'loss_r', 'loss_l')}
 
     def snapshot():
