@@ -17,7 +17,13 @@ the step captured in a hipGraph.
 
 The negatives change every epoch: step(neg) copies them into the fixed [2, n_neg] half of the decoded-edge buffer and
 rebuilds the incidence list on the device (gd_edge_incidence); everything after that is one graph replay, bit-identical to the
-eager step.  Message-passing edges and decoded (positive) edges are separate arguments."""
+eager step.  Message-passing edges and decoded (positive) edges are separate arguments.
+
+NodeClassifierEngine is the same step for NodeClassificationTrainer.train (train_node.py; framework/trainer/base.py:694-752
+upstream): the forward, the backward and Adam are BackboneEngine's, the loss stage is gd_row_nll_f32 over the training rows,
+which writes g = dL/dz directly - no decoded edges, no incidence list, so step() takes no argument and is one graph replay.
+Layer 2's output width is the class count C; where padded_class_width(C) != C the engine trains zero-padded shadows of layer
+2's parameters (the padding stays exactly zero, see _padded_conv2) and refreshes the model's own at the end of every iteration."""
 import torch
 
 from . import _lib, ops
@@ -25,8 +31,20 @@ from ._lib import check, ptr, stream_ptr
 from .capture import capture_iterations
 
 
-def fused_backbone_unsupported(model, args, optimizer):
-    """None when the fused backbone step applies, else the reason it does not (one line)."""
+def padded_class_width(C):
+    """The layer-2 width the node-classification step runs at for C classes: C itself when it is a multiple of 32, the next
+    multiple of 32 below 128 (the widths the matrix-core row kernels take), the next multiple of 4 above that."""
+    C = int(C)
+    if C % 32 == 0:
+        return C
+    return (C + 31) // 32 * 32 if C < 128 else (C + 3) // 4 * 4
+
+
+def fused_backbone_unsupported(model, args, optimizer, task='linkpred'):
+    """None when the fused backbone step applies, else the reason it does not (one line).  task: 'linkpred' (Trainer /
+    RetrainTrainer) or 'nodecls' (NodeClassificationTrainer: the output width is a class count, padded by the engine)."""
+    if task not in ('linkpred', 'nodecls'):
+        raise ValueError(f'fused_backbone_unsupported: task {task!r} (linkpred or nodecls)')
     from .framework.trainer.sampler import data_parallel_world
     from .nn import GATConv, GCNConv
     conv1, conv2 = getattr(model, 'conv1', None), getattr(model, 'conv2', None)
@@ -47,7 +65,12 @@ def fused_backbone_unsupported(model, args, optimizer):
     if {id(p) for p in g['params']} != {id(p) for p in model.parameters()} or not all(p.requires_grad for p in g['params']):
         return 'the optimizer does not hold exactly the model\'s parameters'
     hid, out = conv1.out_channels, conv2.out_channels
-    if hid % 4 or out % 4 or max(hid, out) > 1024:
+    if task == 'nodecls':
+        if out > 256:
+            return f'{out} classes (the fused node-classification step takes up to 256)'
+        if hid % 4 or hid > 1024:
+            return f'hidden width {hid} (a multiple of 4 up to 1024)'
+    elif hid % 4 or out % 4 or max(hid, out) > 1024:
         return f'widths {hid} / {out} (multiples of 4 up to 1024)'
     if conv1.in_channels > 1024 and not ops.mfma_out_width(hid):
         return f'no kernel for a {conv1.in_channels} -> {hid} first product'
@@ -72,6 +95,53 @@ def edge_bce(z, pos, neg, coef=1.0, incidence=None):
     return loss, w[:m_all], (None if w_inc is None else w_inc[:2 * m_all])
 
 
+def row_nll(z, rows, y, d_valid, coef=1.0):
+    """gd_row_nll_f32 on device tensors: F.nll_loss(F.log_softmax(z[:, :d_valid], 1)[rows], y[rows]) over the listed rows (unique
+    node ids; y int64, indexed by node id) -> (loss [1], dz: zeros of z's shape with the listed rows' gradients, times coef)."""
+    L = _lib.lib()
+    rows = rows.to(device=z.device, dtype=torch.int32).contiguous()
+    y = y.to(device=z.device, dtype=torch.int64).contiguous()
+    n, d = int(z.shape[0]), int(z.shape[1])
+    dz = torch.zeros_like(z)
+    loss = torch.empty(1, dtype=torch.float32, device=z.device)
+    ws = torch.empty(max(1, L.gd_row_nll_workspace(rows.numel(), d)), dtype=torch.float32, device=z.device)
+    check(L.gd_row_nll_f32(ptr(z), z.stride(0), n, d, int(d_valid), ptr(rows), rows.numel(), ptr(y), float(coef), ptr(dz),
+                           dz.stride(0), ptr(loss), ptr(ws), stream_ptr(z.device)), 'gd_row_nll_f32')
+    return loss, dz
+
+
+def _padded_conv2(c2, o_pad):
+    """conv2 widened to o_pad output columns by ZEROS (weight rows, bias, attention vectors): the module the step trains in
+    place of a layer whose width is a class count.  The padding stays exactly zero: g = dL/dz is zero behind the class count
+    (gd_row_nll_f32 writes zeros there), so A^T g, dW2, the bias and attention-vector gradients are zero there; t2's padding
+    columns are zero (zero weight rows) and add exact zeros to GAT's row dots; Adam on an all-zero gradient history moves
+    nothing.  The top-left blocks follow the unpadded trajectory: the same products in the same order plus exact zeros."""
+    import torch.nn as nn
+    from .nn import GATConv, GCNConv
+
+    def padded(v, dim):
+        shape = list(v.shape)
+        shape[dim] = o_pad
+        out = torch.zeros(shape, dtype=v.dtype, device=v.device)
+        out.narrow(dim, 0, v.shape[dim]).copy_(v.detach())
+        return nn.Parameter(out, requires_grad=False)
+    if isinstance(c2, GATConv):
+        s2 = GATConv(c2.in_channels, o_pad, c2.negative_slope)
+        s2.lin_src.weight = padded(c2.lin_src.weight, 0)
+        s2.lin_dst = s2.lin_src
+        s2.att_src, s2.att_dst = padded(c2.att_src, -1), padded(c2.att_dst, -1)
+    else:
+        s2 = GCNConv(c2.in_channels, o_pad)
+        s2.lin.weight = padded(c2.lin.weight, 0)
+    s2.bias = padded(c2.bias, 0)
+    return s2
+
+
+def _block(t, like):
+    """The top-left block of t with like's shape."""
+    return t[tuple(slice(0, k) for k in like.shape)]
+
+
 def col_sum(x, row_w=None, gate=None, gated=None, out=None, ws=None):
     """out[j] = sum_r row_w[r] * [gate[r, j] > 0] * x[r, j] (gd_col_sum_f32); gated (may be x): receives the gated matrix."""
     L = _lib.lib()
@@ -92,12 +162,34 @@ class BackboneEngine:
     node features, the message-passing edges, the positive decoded edges (int64 [2, P]) and the number of negatives per epoch."""
 
     def __init__(self, model, x, mp_edges, pos_edges, n_neg, lr, betas, eps, history=4096, use_graph=True):
+        self._setup(model, x, mp_edges, lr, betas, eps, history, use_graph)
+        dev, n, O = self.dev, self.n, self.O
+        L = _lib.lib()
+        f32, i64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int64, device=dev)
+        # the decoded edges [pos | neg]: the positive half is fixed, the negatives' half is rewritten by step()
+        P, n_neg = self.P, self.n_neg = int(pos_edges.shape[1]), int(n_neg)
+        M = self.M = P + n_neg
+        if M < 1:
+            raise ValueError('BackboneEngine: no decoded edges (upstream\'s mean over nothing is NaN)')
+        self.dec = torch.zeros(2, M, **i64)
+        self.dec[:, :P] = pos_edges.to(dev)
+        self.inc_ptr = torch.zeros(n + 1, **i64)
+        self.other = torch.zeros(2 * M, dtype=torch.int32, device=dev)
+        self.src_edge = torch.zeros(2 * M, dtype=torch.int32, device=dev)
+        self.inc_ws = torch.empty(L.gd_edge_incidence_workspace(n, M), dtype=torch.uint8, device=dev)
+        self.w = torch.zeros(M, **f32)
+        self.w_inc = torch.zeros(2 * M, **f32)
+        self.bce_ws = torch.empty(max(1, L.gd_edge_bce_workspace(M, O)), **f32)
+
+    def _setup(self, model, x, mp_edges, lr, betas, eps, history, use_graph, conv2=None):
+        """Everything but the loss stage's buffers.  conv2: the module trained as layer 2 in place of the model's own (a
+        zero-padded shadow, NodeClassifierEngine); self.params are the tensors stepped, self.user_params the model's."""
         from .graph import graph_for
         from .nn import GATConv
         dev = next(model.parameters()).device
         self.dev, self.model = dev, model
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
-        c1, c2 = self.convs = (model.conv1, model.conv2)
+        c1, c2 = self.convs = (model.conv1, model.conv2 if conv2 is None else conv2)
         self.gat = isinstance(c1, GATConv)
         self.x = ops._f32_rows(x.to(dev, torch.float32))
         n = self.n = int(self.x.shape[0])
@@ -107,7 +199,11 @@ class BackboneEngine:
         F_in, H, O = self.F, self.H, self.O = int(self.w1.shape[1]), int(self.w1.shape[0]), int(self.w2.shape[0])
         if H % 4 or O % 4 or max(H, O) > 1024 or int(self.x.shape[1]) != F_in or int(self.w2.shape[1]) != H:
             raise ValueError(f'BackboneEngine: widths {F_in} -> {H} -> {O} (hidden and output: multiples of 4 up to 1024)')
-        self.params = list(model.parameters())
+        self.user_params = list(model.parameters())
+        self.params = self.user_params
+        if conv2 is not None:
+            stepped = dict(conv2.named_parameters())
+            self.params = [stepped[k[len('conv2.'):]] if k.startswith('conv2.') else p for k, p in model.named_parameters()]
         f32, i64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int64, device=dev)
         self.grads = {id(p): torch.zeros_like(p.data) for p in self.params}
         L = _lib.lib()
@@ -146,25 +242,12 @@ class BackboneEngine:
                 self.dyp = torch.zeros(mp, H, **f32)                  # dL/d(x W1^T), zero rows below n
                 self.dw1t = torch.empty(F_in, H, **f32)
                 self.ws_wgrad1 = torch.empty(max(4, L.gd_gemm_f32_workspace(F_in, mp, H)), **f32)
-        # the decoded edges [pos | neg]: the positive half is fixed, the negatives' half is rewritten by step()
-        P, n_neg = self.P, self.n_neg = int(pos_edges.shape[1]), int(n_neg)
-        M = self.M = P + n_neg
-        if M < 1:
-            raise ValueError('BackboneEngine: no decoded edges (upstream\'s mean over nothing is NaN)')
-        self.dec = torch.zeros(2, M, **i64)
-        self.dec[:, :P] = pos_edges.to(dev)
-        self.inc_ptr = torch.zeros(n + 1, **i64)
-        self.other = torch.zeros(2 * M, dtype=torch.int32, device=dev)
-        self.src_edge = torch.zeros(2 * M, dtype=torch.int32, device=dev)
-        self.inc_ws = torch.empty(L.gd_edge_incidence_workspace(n, M), dtype=torch.uint8, device=dev)
-        self.w = torch.zeros(M, **f32)
-        self.w_inc = torch.zeros(2 * M, **f32)
-        self.bce_ws = torch.empty(max(1, L.gd_edge_bce_workspace(M, O)), **f32)
         self.loss = torch.zeros(1, **f32)
         # activations and gradients: static buffers (a captured graph replays from their addresses)
         self.t1, self.p1, self.dx1 = (torch.empty(n, H, **f32) for _ in range(3))
         self.q1 = self.dyp[:n] if (self.wgrad1 == 'xT' and not self.gat) else torch.empty(n, H, **f32)
-        self.t2, self.z, self.g, self.q2 = (torch.empty(n, O, **f32) for _ in range(4))
+        self.t2, self._z, self.q2 = (torch.empty(n, O, **f32) for _ in range(3))
+        self.g = torch.zeros(n, O, **f32)                           # dL/dz (the node-classification loss writes its rows only)
         self.cs_ws = torch.empty(max(4, L.gd_col_sum_workspace(n, max(H, O))), **f32)
         self._bufs = ({}, {})                                       # the GAT layers' row statistics and edge gradients
         self.adam = [{'m': torch.zeros_like(p.data), 'v': torch.zeros_like(p.data),
@@ -208,7 +291,7 @@ class BackboneEngine:
 
     # ---------------------------------------------------------------------------------------------- the fixed-shape step
     def _loss_and_dz(self):
-        L, dev, z, P = _lib.lib(), self.dev, self.z, self.P
+        L, dev, z, P = _lib.lib(), self.dev, self._z, self.P
         check(L.gd_edge_bce_f32(ptr(z), z.stride(0), self.n, self.O, ptr(self.dec), self.M, P, self.dec.data_ptr() + 8 * P, self.M,
                                 self.n_neg, 1.0, ptr(self.w), ptr(self.loss), ptr(self.src_edge), ptr(self.inc_ptr), ptr(self.w_inc),
                                 ptr(self.bce_ws), stream_ptr(dev)), 'gd_edge_bce_f32')
@@ -224,7 +307,7 @@ class BackboneEngine:
         self._first_product(self.t1)
         ops._spmm_raw(g.rowptr, g.col, g.val, self.t1, b1, 0.0, n, g.plan, out=self.p1)
         ops.rows_gemm(self.p1, None, w2, trans_w=True, relu_in=True, out=self.t2)
-        ops._spmm_raw(g.rowptr, g.col, g.val, self.t2, b2, 0.0, n, g.plan, out=self.z)
+        ops._spmm_raw(g.rowptr, g.col, g.val, self.t2, b2, 0.0, n, g.plan, out=self._z)
         self._mark('forward')
         self._loss_and_dz()
         self._mark('loss')
@@ -257,7 +340,7 @@ class BackboneEngine:
         self._first_product(self.t1)
         st1 = self._gat_layer_forward(0, self.t1, self.p1)
         ops.rows_gemm(self.p1, None, w2, trans_w=True, relu_in=True, out=self.t2)
-        st2 = self._gat_layer_forward(1, self.t2, self.z)
+        st2 = self._gat_layer_forward(1, self.t2, self._z)
         self._mark('forward')
         self._loss_and_dz()
         self._mark('loss')
@@ -276,10 +359,14 @@ class BackboneEngine:
             for st, p in zip(self.adam, self.params):
                 check(L.gd_adam_f32(ptr(p.data), ptr(self._grad(p)), ptr(st['m']), ptr(st['v']), ptr(st['step']), p.numel(), self.lr,
                                     self.betas[0], self.betas[1], self.eps, stream_ptr(self.dev)), 'gd_adam_f32')
+            for p, q in zip(self.params, self.user_params):
+                if p is not q:
+                    q.data.copy_(_block(p.data, q))                  # the model's own layer 2 <- the shadow's top-left block
             self._mark('backward')
 
     def _mutable_state(self):
-        state = [p.data for p in self.params] + [self.hist, self.hist_pos]
+        state = [p.data for p in self.params] + [q.data for p, q in zip(self.params, self.user_params) if p is not q]
+        state += [self.hist, self.hist_pos]
         for st in self.adam:
             state += [st['m'], st['v'], st['step']]
         return state
@@ -300,6 +387,9 @@ class BackboneEngine:
                                            ptr(self.src_edge), ptr(self.inc_ws), self.inc_ws.numel(), stream_ptr(self.dev)),
               'gd_edge_incidence')
         self._mark('incidence')
+        self._run_iteration()
+
+    def _run_iteration(self):
         if not self._use_graph:
             self._iteration()
         else:
@@ -309,6 +399,11 @@ class BackboneEngine:
         for st in self.adam:
             st['steps'] += 1
         self.steps_done += 1
+
+    @property
+    def z(self):
+        """The latest forward's output, [n, layer 2's own width] (a view of the engine's buffer)."""
+        return self._z[:, :int(self.model.conv2.out_channels)]
 
     def last_loss(self):
         """train_loss of the latest step: one blocking host read."""
@@ -325,19 +420,57 @@ class BackboneEngine:
 
     # ---------------------------------------------------------------------------------------------- optimizer state
     def import_adam_state(self, optimizer):
-        for st, p in zip(self.adam, self.params):
+        for st, p in zip(self.adam, self.user_params):
             have = optimizer.state.get(p)
             if have and 'exp_avg' in have:
-                st['m'].copy_(have['exp_avg'])
-                st['v'].copy_(have['exp_avg_sq'])
+                for mine, theirs in ((st['m'], have['exp_avg']), (st['v'], have['exp_avg_sq'])):
+                    mine.zero_()                                     # (a shadow's padding: zero moments)
+                    _block(mine, p).copy_(theirs)
                 st['steps'] = int(have['step'])
                 st['step'].fill_(st['steps'])
 
     def export_adam_state(self, optimizer):
         """Adam moments and step count of every parameter into the caller's optimizer; the gradients are not kept (the
         autograd loop's zero_grad after the step)."""
-        for st, p in zip(self.adam, self.params):
+        for st, p in zip(self.adam, self.user_params):
             if st['steps']:
-                optimizer.state[p] = {'step': torch.tensor(float(st['steps'])), 'exp_avg': st['m'].clone(),
-                                      'exp_avg_sq': st['v'].clone()}
+                optimizer.state[p] = {'step': torch.tensor(float(st['steps'])), 'exp_avg': _block(st['m'], p).clone(),
+                                      'exp_avg_sq': _block(st['v'], p).clone()}
             p.grad = None
+
+
+class NodeClassifierEngine(BackboneEngine):
+    """One node-classifier training request (NodeClassificationTrainer.train): model (GCN / GAT whose output width is the class
+    count C <= 256), node features, the message-passing edges, the labels y (int64, by node id) and the boolean train mask.
+    With padded_class_width(C) == C every parameter is stepped in place; otherwise layer 2 is trained on zero-padded shadows
+    (self.shadows: parameter name -> padded tensor) and the model's own tensors are refreshed inside every iteration."""
+
+    def __init__(self, model, x, edge_index, y, train_mask, lr, betas, eps, history=4096, use_graph=True):
+        dev = next(model.parameters()).device
+        C = self.C = int(model.conv2.out_channels)
+        if C > 256:
+            raise ValueError(f'NodeClassifierEngine: {C} classes (up to 256)')
+        rows = train_mask.to(dev).nonzero().flatten()
+        if rows.numel() < 1:
+            raise ValueError('NodeClassifierEngine: an empty train mask (upstream\'s mean over nothing is NaN)')
+        y = y.to(dev, torch.int64).contiguous()
+        if y.numel() != int(x.shape[0]) or int(y[rows].min()) < 0 or int(y[rows].max()) >= C:
+            raise ValueError(f'NodeClassifierEngine: a training row\'s label lies outside [0, {C})')
+        o_pad = padded_class_width(C)
+        shadow = _padded_conv2(model.conv2, o_pad).to(dev) if o_pad != C else None
+        self._setup(model, x, edge_index, lr, betas, eps, history, use_graph, conv2=shadow)
+        self.shadows = {k: p for (k, q), p in zip(model.named_parameters(), self.params) if p is not q}
+        self.y, self.rows = y, rows.to(torch.int32).contiguous()
+        self.nll_ws = torch.empty(max(1, _lib.lib().gd_row_nll_workspace(self.rows.numel(), self.O)), dtype=torch.float32, device=dev)
+
+    def _loss_and_dz(self):
+        L, dev, z, g = _lib.lib(), self.dev, self._z, self.g
+        check(L.gd_row_nll_f32(ptr(z), z.stride(0), self.n, self.O, self.C, ptr(self.rows), self.rows.numel(), ptr(self.y), 1.0,
+                               ptr(g), g.stride(0), ptr(self.loss), ptr(self.nll_ws), stream_ptr(dev)), 'gd_row_nll_f32')
+        check(L.gd_edgeprob_record_f32(ptr(self.loss), None, 1.0, 0.0, ptr(self.hist), self.hist.shape[0], ptr(self.hist_pos),
+                                       stream_ptr(dev)), 'gd_edgeprob_record_f32')
+
+    def step(self):
+        """One epoch: one graph replay."""
+        self._mark('start')
+        self._run_iteration()

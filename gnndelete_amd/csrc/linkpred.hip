@@ -5,9 +5,11 @@
 //                     gradients, the gradients also gathered into incidence order for gd_edge_dot_bwd_f32;
 //   gd_col_sum_f32    out[j] = sum_r row_w[r] * [gate[r, j] > 0] * x[r, j]: the bias gradients (dy.sum(0)), the gated form (which
 //                     can also store the gated matrix: the ReLU backward and its bias gradient in one pass) and GATConv's
-//                     attention-vector gradients.
+//                     attention-vector gradients;
+//   gd_row_nll_f32    F.nll_loss(F.log_softmax(z[:, :d_valid], 1)[rows], y[rows]) over a list of rows, value and logit gradients:
+//                     the loss stage of the fused node-classification step (NodeClassificationTrainer.train, base.py:694-752).
 //
-// Both are streams.  Everything that is summed is summed in a fixed order (per-block partials, then one pass in block order):
+// All are streams.  Everything that is summed is summed in a fixed order (per-block partials, then one pass in block order):
 // no atomics, the same bits on every call.
 #include "common.h"
 
@@ -15,6 +17,7 @@ namespace gd {
 
 constexpr int kBceMaxBlocks = 2048;      // partials the finishing thread adds; blocks walk the edges grid-strided beyond that
 constexpr int kColSumMaxBlocks = 512;
+constexpr int kNllMaxBlocks = 1024;      // as kBceMaxBlocks, for the listed rows of gd_row_nll_f32
 
 // One lane group (LPR lanes) per decoded edge k < M = n_pos + n_neg, edges taken grid-strided: l_k = <z[a_k], z[b_k]>, an
 // endpoint outside [0, n) makes it 0 (nothing outside z is read).  Stable forms with e = exp(-|l|):
@@ -129,6 +132,98 @@ __global__ __launch_bounds__(256) void col_sum_finish_kernel(const float* __rest
   }
 }
 
+template <int LPR>
+__device__ __forceinline__ float group_max(float v) {
+#pragma unroll
+  for (int off = 1; off < LPR; off <<= 1) v = fmaxf(v, __shfl_xor(v, off));
+  return v;
+}
+
+// One lane group (LPR lanes, a float4 per lane) per listed row i < n_sel, rows taken grid-strided: u = row_idx[i], label y[u].
+//     term = logsumexp(z[u, :d_valid]) - z[u, y[u]];    dz[u, j] = scale (softmax(z[u, :d_valid])_j - [j == y[u]]),  0 for j >= d_valid
+// with the row maximum subtracted, in forms that keep a confident row's tiny term and gradient (no lse - z_y, no 1 - 1).  A label outside [0, d_valid) gives term = 0 and a zero dz row; a row id outside [0, n_rows) is
+// skipped (nothing outside z / dz is touched).  The trip count is wave-uniform and a tail group works on a clamped row it does not
+// write, so every lane of a wave executes every cross-lane step.
+template <int LPR>
+__global__ __launch_bounds__(256) void row_nll_kernel(const float* __restrict__ z, int64_t ld_z, int64_t n_rows, int32_t d4,
+                                                      int32_t d_valid, const int32_t* __restrict__ row_idx, int64_t n_sel,
+                                                      const int64_t* __restrict__ y, float scale, float* __restrict__ dz,
+                                                      int64_t ld_dz, float* __restrict__ partials) {
+  constexpr int G = kWave / LPR;
+  __shared__ float red[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane / LPR, li = lane % LPR;
+  const int64_t per_pass = (int64_t)gridDim.x * 4 * G;
+  float sum = 0.f;
+  for (int64_t base = ((int64_t)blockIdx.x * 4 + wave) * G; base < n_sel; base += per_pass) {
+    const int64_t i = base + g;
+    const bool mine = i < n_sel;
+    const int64_t u = row_idx[mine ? i : n_sel - 1];
+    const bool ok = u >= 0 && u < n_rows;
+    const bool in = ok && li < d4;
+    const int64_t label = ok ? y[u] : -1;
+    const bool labelled = label >= 0 && label < d_valid;
+    const float4 zv = in ? reinterpret_cast<const float4*>(z + u * ld_z)[li] : f4_zero();
+    const float zz[4] = {zv.x, zv.y, zv.z, zv.w};
+    bool valid[4];
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      valid[k] = in && li * 4 + k < d_valid;
+      m = fmaxf(m, valid[k] ? zz[k] : -INFINITY);
+    }
+    m = group_max<LPR>(m);
+    if (!ok) m = 0.f;
+    // rest = the sum without the label's term, ey = the label's term, zy = its logit (one non-zero lane entry each: exact sums)
+    float e[4], rest = 0.f, ey = 0.f, zy = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      e[k] = valid[k] ? expf(zz[k] - m) : 0.f;
+      const bool at = valid[k] && li * 4 + k == label;
+      rest += at ? 0.f : e[k];
+      ey += at ? e[k] : 0.f;
+      zy += at ? zz[k] : 0.f;
+    }
+    rest = lanes_sum<LPR>(rest);
+    ey = lanes_sum<LPR>(ey);
+    zy = lanes_sum<LPR>(zy);
+    float se = rest + ey;
+    if (!ok) se = 1.f;
+    // -log softmax_y = log(1 + rest / ey): as it stands while ey has not left the normal range (a confident row has a term far
+    // below 1 ulp of its logits), m - zy + log(se) beyond that
+    if (mine && labelled && li == 0) sum += (m - zy < 10.f) ? log1pf(rest / ey) : (m - zy) + logf(se);
+    if (mine && in) {
+      const float r = labelled ? scale / se : 0.f;
+      float gr[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        gr[k] = r * e[k];
+        if (labelled && li * 4 + k == label) gr[k] = -r * rest;       // softmax_y - 1 = -rest / se, without the 1 - 1
+      }
+      reinterpret_cast<float4*>(dz + u * ld_dz)[li] = make_float4(gr[0], gr[1], gr[2], gr[3]);
+    }
+  }
+  sum = wave_sum(sum);
+  if (lane == 0) red[wave] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// loss = (1/n_sel) * the partials added in block order by one thread (in fp64: up to 1,024 partials of like sign)
+__global__ void row_nll_finish_kernel(const float* __restrict__ partials, int32_t n_part, double inv_n, float* __restrict__ loss) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    double s = 0.0;
+    for (int32_t i = 0; i < n_part; ++i) s += (double)partials[i];
+    *loss = (float)(s * inv_n);
+  }
+}
+
+static inline int nll_blocks(int64_t n_sel, int lpr) {
+  const int64_t per_block = 4 * (kWave / lpr);
+  const int64_t nb = (n_sel + per_block - 1) / per_block;
+  return (int)(nb > kNllMaxBlocks ? kNllMaxBlocks : nb);
+}
+
 static inline int bce_blocks(int64_t m_all, int lpr) {
   const int64_t per_block = 4 * (kWave / lpr);
   const int64_t nb = (m_all + per_block - 1) / per_block;
@@ -218,4 +313,46 @@ extern "C" int gd_col_sum_f32(const float* x, int64_t ld, int64_t n_rows, int32_
   }
   hipLaunchKernelGGL(col_sum_finish_kernel, dim3(1), dim3(256), 0, s, workspace, nb, d, out);
   return launched("col_sum_finish");
+}
+
+extern "C" int64_t gd_row_nll_workspace(int64_t n_sel, int32_t d) {
+  using namespace gd;
+  if (n_sel <= 0 || d < 4 || d % 4 || d > 256) return 1;
+  return nll_blocks(n_sel, lanes_per_row(d / 4));
+}
+
+extern "C" int gd_row_nll_f32(const float* z, int64_t ld_z, int64_t n_rows, int32_t d, int32_t d_valid, const int32_t* row_idx,
+                              int64_t n_sel, const int64_t* y, float coef, float* dz, int64_t ld_dz, float* loss, float* workspace,
+                              void* stream) {
+  using namespace gd;
+  GD_REQUIRE(n_sel >= 1 && n_sel < (1ll << 31), GD_E_DIM, "gd_row_nll_f32: n_sel=%lld (the mean over no rows is NaN upstream)",
+             (long long)n_sel);
+  GD_REQUIRE(d >= 4 && d <= 256 && d % 4 == 0, GD_E_DIM, "gd_row_nll_f32: d=%d must be a multiple of 4 in [4, 256]", d);
+  GD_REQUIRE(d_valid >= 1 && d_valid <= d, GD_E_DIM, "gd_row_nll_f32: d_valid=%d must lie in [1, d=%d]", d_valid, d);
+  GD_REQUIRE(n_rows >= 1 && n_rows < (1ll << 31) && ld_z >= d && ld_z % 4 == 0 && ld_dz >= d && ld_dz % 4 == 0, GD_E_DIM,
+             "gd_row_nll_f32: n_rows=%lld, row pitches %lld / %lld must be multiples of 4, at least d=%d", (long long)n_rows,
+             (long long)ld_z, (long long)ld_dz, d);
+  GD_REQUIRE(z && row_idx && y && dz && loss && workspace, GD_E_NULL, "gd_row_nll_f32: null pointer");
+  GD_REQUIRE(aligned16(z) && aligned16(dz), GD_E_ALIGN, "gd_row_nll_f32: unaligned matrix");
+  hipStream_t s = (hipStream_t)stream;
+  const int d4 = d / 4;
+  const int lpr = lanes_per_row(d4);
+  const int nb = nll_blocks(n_sel, lpr);
+  const float scale = coef / (float)n_sel;
+#define GD_NLL_CASE(LPR) \
+  hipLaunchKernelGGL((row_nll_kernel<LPR>), dim3(nb), dim3(256), 0, s, z, ld_z, n_rows, d4, d_valid, row_idx, n_sel, y, scale, dz, ld_dz, workspace)
+  switch (lpr) {
+    case 1: GD_NLL_CASE(1); break;
+    case 2: GD_NLL_CASE(2); break;
+    case 4: GD_NLL_CASE(4); break;
+    case 8: GD_NLL_CASE(8); break;
+    case 16: GD_NLL_CASE(16); break;
+    case 32: GD_NLL_CASE(32); break;
+    default: GD_NLL_CASE(64); break;
+  }
+#undef GD_NLL_CASE
+  int rc = launched("row_nll");
+  if (rc) return rc;
+  hipLaunchKernelGGL(row_nll_finish_kernel, dim3(1), dim3(64), 0, s, workspace, nb, 1.0 / (double)n_sel, loss);
+  return launched("row_nll_finish");
 }

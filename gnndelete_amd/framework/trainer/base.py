@@ -74,12 +74,12 @@ class Trainer:
         return self.train_fullbatch(model, data, optimizer, args)
 
     # ------------------------------------------------------------------ --fused_backbone (gnndelete_amd/backbone.py)
-    def _fused_backbone_applies(self, model, optimizer, args):
+    def _fused_backbone_applies(self, model, optimizer, args, task='linkpred'):
         """Does this run take the fused backbone step?  With the flag, trainer_log['backbone_step'] says 'fused' or why not."""
         if not getattr(args, 'fused_backbone', False):
             return False
         from ...backbone import fused_backbone_unsupported
-        reason = fused_backbone_unsupported(model, args, optimizer)
+        reason = fused_backbone_unsupported(model, args, optimizer, task)
         self.trainer_log['backbone_step'] = 'fused' if reason is None else reason
         if reason is not None:
             print(f'--fused_backbone: {reason}; running the autograd loop', flush=True)
@@ -302,28 +302,54 @@ class Trainer:
 class NodeClassificationTrainer(Trainer):
     """NLL node classification (base.py:694-864); eval = accuracy + micro-F1 on val_mask."""
 
+    def _classifier_engine(self, model, data, optimizer, args):
+        """The engine of one train call (--fused_backbone): Adam's hyper-parameters and state from the caller's optimizer (a
+        second train call on the same model and optimizer continues the first)."""
+        from ...backbone import NodeClassifierEngine
+        from .gnndelete_nodeemb import _adam_hyper
+        lr, betas, eps = _adam_hyper(optimizer)
+        engine = NodeClassifierEngine(model, data.x, data.edge_index.contiguous(), data.y, data.train_mask, lr, betas, eps,
+                                      history=max(16, args.epochs))
+        engine.import_adam_state(optimizer)
+        self._backbone = engine
+        return engine
+
     def train(self, model, data, optimizer, args):
         _require_gpu()
         start = time.time()
         best_epoch, best_valid_acc = 0, 0
         model = model.to(device)
         data = data.to(device)
+        engine = None
+        if self._fused_backbone_applies(model, optimizer, args, task='nodecls'):
+            engine = self._classifier_engine(model, data, optimizer, args)
         for epoch in range(args.epochs):
             model.train()
-            z = F.log_softmax(model(data.x, data.edge_index), dim=1)
-            loss = F.nll_loss(z[data.train_mask], data.y[data.train_mask])
-            loss.backward()
-            optimizer.step()
-            optimizer.zero_grad()
+            if engine is not None:
+                engine.step()
+            else:
+                z = F.log_softmax(model(data.x, data.edge_index), dim=1)
+                loss = F.nll_loss(z[data.train_mask], data.y[data.train_mask])
+                loss.backward()
+                optimizer.step()
+                optimizer.zero_grad()
             if (epoch + 1) % args.valid_freq == 0:
+                if engine is not None:
+                    train_loss = engine.last_loss()                 # the block's host read
+                    z = F.log_softmax(engine.z, dim=1)              # this epoch's forward, as the loop keeps it
+                    engine.export_adam_state(optimizer)             # (a checkpoint below carries the optimizer's state)
+                else:
+                    train_loss = loss.item()
                 valid_loss, dt_acc, dt_f1, valid_log = self.eval(model, data, 'val')
-                self._record({'epoch': epoch, 'train_loss': loss.item()}, valid_log)
+                self._record({'epoch': epoch, 'train_loss': train_loss}, valid_log)
                 if dt_acc > best_valid_acc:
                     best_valid_acc, best_epoch = dt_acc, epoch
                     print(f'Save best checkpoint at epoch {epoch:04d}. Valid Acc = {dt_acc:.4f}')
                     torch.save({'model_state': model.state_dict(), 'optimizer_state': optimizer.state_dict()},
                                os.path.join(args.checkpoint_dir, 'model_best.pt'))
                     torch.save(z.detach(), os.path.join(args.checkpoint_dir, 'node_embeddings.pt'))
+        if engine is not None:
+            engine.export_adam_state(optimizer)
         self.trainer_log['training_time'] = time.time() - start
         torch.save({'model_state': model.state_dict(), 'optimizer_state': optimizer.state_dict()},
                    os.path.join(args.checkpoint_dir, 'model_final.pt'))

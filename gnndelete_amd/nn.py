@@ -66,6 +66,11 @@ class GATConv(nn.Module):
         h = self.lin_src(x, const_x=not x.requires_grad)
         a_src = (h * self.att_src.view(1, -1)).sum(-1)
         a_dst = (h * self.att_dst.view(1, -1)).sum(-1)
+        pad = -self.out_channels % 4
+        if pad:
+            # a class count such as 3 or 7 (train_node.py): the aggregation kernels take multiples of 4 - zero columns in, cut off again
+            out = ops.gat_aggregate(F.pad(h, (0, pad)), a_src, a_dst, g, F.pad(self.bias, (0, pad)), self.negative_slope)
+            return out[:, :self.out_channels]
         return ops.gat_aggregate(h, a_src, a_dst, g, self.bias, self.negative_slope)
 
 

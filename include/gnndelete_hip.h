@@ -47,7 +47,8 @@ extern "C" {
                                 gd_edgeprob_dec_f32, gd_edge_incidence (+ their _workspace queries), gd_rows_add_f32, gd_edgeprob_record_f32:
                                 the fused edge-probability step (entries added, none changed: the version stays);
                                 gd_rowfold_loss_f32 (+ _blocks), gd_rowfold_kld_scale_f32: the folded KLD / cosine row losses (entries added: the version stays);
-                                gd_edge_bce_f32, gd_col_sum_f32 (+ their _workspace queries): the fused backbone step (entries added: the version stays) */
+                                gd_edge_bce_f32, gd_col_sum_f32 (+ their _workspace queries): the fused backbone step (entries added: the version stays);
+                                gd_row_nll_f32 (+ its _workspace query): the fused node-classification step (entries added: the version stays) */
 
 enum {
   GD_OK = 0,
@@ -768,6 +769,26 @@ int gd_edge_bce_f32(const float* z, int64_t ld_z, int64_t n_nodes, int32_t d, co
 int64_t gd_col_sum_workspace(int64_t n_rows, int32_t d);
 int gd_col_sum_f32(const float* x, int64_t ld, int64_t n_rows, int32_t d, const float* row_w, const float* gate, float* gated,
                    float* out, float* workspace, void* stream);
+
+/* The loss stage of the fused node-classification step (NodeClassificationTrainer.train, framework/trainer/base.py:694-752):
+ * F.nll_loss(F.log_softmax(z[:, :d_valid], 1)[rows], y[rows]) (mean reduction) and its logit gradients over the n_sel listed
+ * rows u = row_idx[i] of a pitched [n_rows, d] matrix:
+ *     loss[0] = (1/n_sel) sum_i ( logsumexp(z[u, :d_valid]) - z[u, y[u]] )             (NOT scaled by coef, as gd_edge_bce_f32's)
+ *     dz[u, j] = coef / n_sel * (softmax(z[u, :d_valid])_j - [j == y[u]])  for j < d_valid,   0 for d_valid <= j < d
+ * The row maximum is subtracted; expf / logf in fp32, the label's term as log1p(sum_{j != y} e_j / e_y) and its gradient as
+ * -sum_{j != y} e_j / sum_j e_j (a confident row keeps its tiny term and gradient: no lse - z_y, no 1 - 1).  Only the d columns of the listed rows of dz are written: a caller that
+ * wants dL/dz of the whole matrix zeroes dz once.  row_idx (int32) must be unique (two entries of one row would race on its dz
+ * row); it need not be ascending.  y is indexed by node id (int64 [n_rows]).  A label outside [0, d_valid) reads nothing
+ * outside the row: its row adds nothing to the sum and gets a ZERO dz row, but still counts in n_sel (F.nll_loss raises there;
+ * callers reject such labels).  A row id outside [0, n_rows) is skipped the same way.  One lane group per row, float4 per
+ * lane; at most 1,024 blocks, which walk the rows grid-strided; one partial per block, added in block order by one thread (no
+ * float atomics): the same bits every call.  d % 4 == 0, 4 <= d <= 256, 1 <= d_valid <= d, pitches % 4 == 0 and >= d,
+ * n_sel >= 1 (upstream's mean over nothing is NaN) - GD_E_DIM otherwise; 16-byte aligned z / dz - GD_E_ALIGN otherwise.
+ * workspace: gd_row_nll_workspace(n_sel, d) floats (= the number of blocks).  Two launches, graph-capturable. */
+int64_t gd_row_nll_workspace(int64_t n_sel, int32_t d);
+int gd_row_nll_f32(const float* z, int64_t ld_z, int64_t n_rows, int32_t d, int32_t d_valid, const int32_t* row_idx,
+                   int64_t n_sel, const int64_t* y, float coef, float* dz, int64_t ld_dz, float* loss, float* workspace,
+                   void* stream);
 
 /* ---------------------------------------------------------------- optimizer ------------ */
 
