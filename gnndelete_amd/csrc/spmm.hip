@@ -443,6 +443,214 @@ __global__ __launch_bounds__(256) void spmm_persist_aux_kernel(const int4* __res
                                                  nnz, perm, aux, aux_sum);
 }
 
+// ---------------------------------------------------------------------------------------------
+// WIDE form of the one-launch sweep for rows of exactly 64 floats (gd_spmm_csr_onepass_wide_f32): an item is up to 16
+// CONSECUTIVE light rows (adjacent in the plan, in node ids and in the CSR, <= 64 in-edges together) and its row sums are formed
+// on the matrix pipe, Y[16 x 64] = S[16 x E] . X[E x 64]: X = the gathered source rows, S holds in column e edge e's weight in
+// the row of the output row the edge belongs to and zeros elsewhere.  The lane layout of the 64-float sweep IS the operand
+// layout of v_mfma_f32_16x16x4_f32: a trip loads one float4 per lane, lane group g = lane >> 4 on edge slot 4t + g, li = lane & 15
+// on features 4 li .. 4 li + 3 - the B coordinates (k = lane >> 4, n = lane & 15) - so a trip is four matrix instructions, one
+// per float4 component c, with A = (local row of edge 4t + g == li) ? weight : 0; lane (n, q = lane >> 4) ends with
+// acc_c[j] = y[row + 4q + j][4n + c] and writes four float4, 256 contiguous bytes per row and lane group.  No cross-lane
+// reduction, no per-row accumulator sets, no select-and-FMA pairs; the per-visit work (descriptor, prefetch, epilogue) is shared
+// by up to 16 rows.  The local row of an edge (0 .. 15) travels in bits 24 .. 27 of the index array (`colt`, built per plan: the
+// source id needs 24 bits under the 24-bit addressing conditions this form requires); every use of an index masks it off.
+// Items: {first row, start, end, -(16 + rows - 1)}; {row, start, end, -2} = GROUP member of a hub row (> 64 in-edges) on the
+// vector path of spmm_persist_body<16, 1, 4> - same trips, same summation order, same bits; {-1, 0, 0, -1} = padding.
+// The fp32 matrix instruction is bitwise an fmaf chain in k order and fmaf(0, x, acc) == acc for finite x, so a row's sum is the
+// fmaf chain over its own edges in item order starting from the bias (then + self_coef * x_self[row]): deterministic, associated
+// differently from the lane-group sums of the vector forms.  NON-FINITE CAVEAT: 0 x Inf = NaN inside the instruction, so a source
+// row that holds Inf or NaN poisons EVERY row of the items that gather it, not only its true neighbours.
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+// block cap of the wide launch (GD_SPMM_GRID_CAP overrides it per call).  The bench graph has 40 k items = 10 k blocks; measured
+// in the bench step (spmm2 / spmm2_t, us): cap 4096 52.2 / 56.1, 8192 51.3 / 55.1, no cap 52.1 / 55.4 (profiles/spmm_wide_ab.txt)
+#ifndef GD_SPMM_WIDE_GRID_CAP
+#define GD_SPMM_WIDE_GRID_CAP 8192
+#endif
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void spmm_wide_kernel(
+    const int4* __restrict__ items, int32_t n_items, const int32_t* __restrict__ xcd_bounds, const int32_t* __restrict__ colt,
+    const float* __restrict__ val, const float* __restrict__ x, int64_t ldx, float* __restrict__ y, int64_t ldy,
+    const float* __restrict__ bias, float self_coef, const float* __restrict__ xs, int32_t nnz) {
+  constexpr int kXcd = 8, U = 4;
+  constexpr int kSrcMask = (1 << 24) - 1;
+  const int lane = threadIdx.x & 63;
+  const int g = lane >> 4, li = lane & 15;
+  const int xcd = blockIdx.x % kXcd;
+  const int stride = (gridDim.x / kXcd) * 4;                        // waves per XCD
+  const int wx = (blockIdx.x / kXcd) * 4 + (threadIdx.x >> 6);
+  const int i0 = xcd_bounds[xcd], i1 = xcd_bounds[xcd + 1];
+  // (the barrier invariant of the group path, checked where it costs the sweep no register: spmm_persist_body)
+  if ((i0 | i1) & 3) __builtin_trap();
+  const uint32_t lo = 16u * (uint32_t)li;
+  const uint32_t pitch_b = (uint32_t)ldx * 4u, pitch_y = (uint32_t)ldy * 4u;
+  const char* xb = reinterpret_cast<const char*>(x);
+
+  // (the wave's item index is wave-uniform: said so to the compiler, the descriptors are scalar loads into SGPRs - no lane-0
+  //  fetch, no vector registers held for them)
+  int i = __builtin_amdgcn_readfirstlane(i0 + wx);
+  if (i >= i1) return;
+  // descriptor two visits ahead, (index, weight) one visit ahead, as in spmm_persist_body
+  int4 d0 = items[i], d1 = items[min(i + stride, i1 - 1)];          // {row, start, end, slot}
+  int kk = min(d0.y + lane, nnz - 1);
+  int c = colt[kk];
+  float w = val ? val[kk] : 1.0f;
+  __shared__ float4 grp_red[4][16];
+  // the bias (zeros without one) waits in LDS: an item starts its accumulators with one ds_read, no register or address is held
+  // for it across the sweep
+  __shared__ float4 bias_s[16];
+  if (threadIdx.x < 16) bias_s[threadIdx.x] = bias ? reinterpret_cast<const float4*>(bias)[threadIdx.x] : f4_zero();
+  __syncthreads();
+  for (; i < i1; i += stride) {
+    const int row = d0.x, slot = d0.w;
+    const int c_now = c;
+    const float w_now = w;
+    const int4 d2 = items[min(i + 2 * stride, i1 - 1)];
+    kk = min(d1.y + lane, nnz - 1);
+    c = colt[kk];
+    w = val ? val[kk] : 1.0f;
+    if (slot != -2) {
+      // ---- up to 16 light rows on the matrix pipe
+      const int nr = -slot - 15;                         // rows of the item (<= 0: padding)
+      const int cnt = d0.z - d0.y;
+      const float w_cur = lane < cnt ? w_now : 0.f;
+      const int trips = (cnt + 3) >> 2;
+      // (padding slots of the last trip re-read the item's last neighbour and take weight 0 from lane `cnt`)
+      const int last4 = 4 * cnt - 4, end4 = 4 * cnt;
+      const float4 bv = bias_s[li];
+      f32x4_t a0 = {bv.x, bv.x, bv.x, bv.x}, a1 = {bv.y, bv.y, bv.y, bv.y}, a2 = {bv.z, bv.z, bv.z, bv.z}, a3 = {bv.w, bv.w, bv.w, bv.w};
+      auto fetch = [&](int t, float4& xv, float& av) {
+        const int j4 = 16 * t + 4 * g;
+        const int cs = __builtin_amdgcn_ds_bpermute(min(j4, last4), c_now);
+        const float wj = __int_as_float(__builtin_amdgcn_ds_bpermute(min(j4, end4), __float_as_int(w_cur)));
+        av = ((uint32_t)cs >> 24) == (uint32_t)li ? wj : 0.f;
+        const uint32_t ro = __umul24((uint32_t)(cs & kSrcMask), pitch_b);
+        xv = *reinterpret_cast<const float4*>(xb + (ro + lo));
+      };
+      auto mma = [&](float av, const float4& xv) {
+        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xv.x, a0, 0, 0, 0);
+        a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xv.y, a1, 0, 0, 0);
+        a2 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xv.z, a2, 0, 0, 0);
+        a3 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xv.w, a3, 0, 0, 0);
+      };
+      int t0 = 0;
+      for (; t0 + U <= trips; t0 += U) {
+        float4 xv[U];
+        float av[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) fetch(t0 + u, xv[u], av[u]);
+        __builtin_amdgcn_sched_barrier(0);               // all four loads in flight before the first matrix instruction waits
+#pragma unroll
+        for (int u = 0; u < U; ++u) mma(av[u], xv[u]);
+      }
+      // the last one to three trips, each count in a block of its own (a value defined and used under `u < rem` would stay
+      // allocated around the whole sweep)
+      const int rem = trips - t0;
+      if (rem == 1) {
+        float4 xv;
+        float av;
+        fetch(t0, xv, av);
+        mma(av, xv);
+      } else if (rem == 2) {
+        float4 xv[2];
+        float av[2];
+        fetch(t0, xv[0], av[0]);
+        fetch(t0 + 1, xv[1], av[1]);
+        mma(av[0], xv[0]);
+        mma(av[1], xv[1]);
+      } else if (rem == 3) {
+        float4 xv[3];
+        float av[3];
+        fetch(t0, xv[0], av[0]);
+        fetch(t0 + 1, xv[1], av[1]);
+        fetch(t0 + 2, xv[2], av[2]);
+        mma(av[0], xv[0]);
+        mma(av[1], xv[1]);
+        mma(av[2], xv[2]);
+      }
+      // lane (n = li, q = g) holds rows row + 4q + j, features 4n .. 4n + 3; rows past the item's are not stored
+      const uint32_t r0 = (uint32_t)(row + 4 * g);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (4 * g + j < nr) {
+          float4 o = make_float4(a0[j], a1[j], a2[j], a3[j]);
+          if (self_coef != 0.0f)
+            o = f4_fma(self_coef, *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(xs) + (__umul24(r0 + j, pitch_b) + lo)), o);
+          *reinterpret_cast<float4*>(reinterpret_cast<char*>(y) + (__umul24(r0 + j, pitch_y) + lo)) = o;
+        }
+      }
+    } else {
+      // ---- GROUP member of a hub row: the vector path of spmm_persist_body<16, 1, 4>, trip for trip (block-uniform branch: the
+      //      planner aligns the quadruples and the XCD ranges to 4)
+      int base = d0.y;
+      int c_cur = c_now;
+      float w_raw = w_now;
+      float4 acc = f4_zero();
+      for (;;) {
+        const int cnt = min(kWave, d0.z - base);
+        const float w_cur = lane < cnt ? w_raw : 0.f;
+        const int trips = (cnt + 3) >> 2;
+        const int last4 = 4 * cnt - 4, end4 = 4 * cnt;
+        auto fetch = [&](int t, float4& xv, float& wj) {
+          const int j4 = 16 * t + 4 * g;
+          const int cs = __builtin_amdgcn_ds_bpermute(min(j4, last4), c_cur);
+          wj = __int_as_float(__builtin_amdgcn_ds_bpermute(min(j4, end4), __float_as_int(w_cur)));
+          const uint32_t ro = __umul24((uint32_t)(cs & kSrcMask), pitch_b);
+          xv = *reinterpret_cast<const float4*>(xb + (ro + lo));
+        };
+        int t0 = 0;
+        for (; t0 + U <= trips; t0 += U) {
+          float4 xv[U];
+          float wj[U];
+#pragma unroll
+          for (int u = 0; u < U; ++u) fetch(t0 + u, xv[u], wj[u]);
+#pragma unroll
+          for (int u = 0; u < U; ++u) acc = f4_fma(wj[u], xv[u], acc);
+        }
+        const int rem = trips - t0;
+        if (rem == 1) {
+          float4 xv;
+          float wj;
+          fetch(t0, xv, wj);
+          acc = f4_fma(wj, xv, acc);
+        } else if (rem == 2) {
+          float4 xv[2];
+          float wj[2];
+          fetch(t0, xv[0], wj[0]);
+          fetch(t0 + 1, xv[1], wj[1]);
+          acc = f4_fma(wj[1], xv[1], f4_fma(wj[0], xv[0], acc));
+        } else if (rem == 3) {
+          float4 xv[3];
+          float wj[3];
+          fetch(t0, xv[0], wj[0]);
+          fetch(t0 + 1, xv[1], wj[1]);
+          fetch(t0 + 2, xv[2], wj[2]);
+          acc = f4_fma(wj[2], xv[2], f4_fma(wj[1], xv[1], f4_fma(wj[0], xv[0], acc)));
+        }
+        base += kWave;
+        if (base >= d0.z) break;
+        const int k2 = min(base + lane, nnz - 1);
+        c_cur = colt[k2];
+        w_raw = val ? val[k2] : 1.0f;
+      }
+      acc = f4_group_sum<16>(acc);
+      const int wave = threadIdx.x >> 6;
+      if (g == 0) grp_red[wave][li] = acc;
+      __syncthreads();
+      if (wave == 0 && g == 0) {
+        float4 o = f4_add(f4_add(f4_add(grp_red[0][li], grp_red[1][li]), grp_red[2][li]), grp_red[3][li]);
+        if (self_coef != 0.0f)
+          o = f4_fma(self_coef, *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(xs) + (__umul24((uint32_t)row, pitch_b) + lo)), o);
+        if (bias) o = f4_add(o, bias_s[li]);
+        *reinterpret_cast<float4*>(reinterpret_cast<char*>(y) + (__umul24((uint32_t)row, pitch_y) + lo)) = o;
+      }
+      __syncthreads();
+    }
+    d0 = d1;
+    d1 = d2;
+  }
+}
+
 __global__ __launch_bounds__(256) void spmm_fixup_kernel(const int4* __restrict__ split, int32_t n_split,
                                                          const float* __restrict__ scratch,
                                                          const float* __restrict__ x, int64_t ldx,
@@ -615,20 +823,14 @@ static int launch_persist(const int32_t* items, int32_t n_items, const int32_t* 
       else GD_ITEMS_LAUNCH(LPR, VPL, false, false);                                                                \
     }                                                                                                              \
   } while (0)
-  // LAB (round 6): the 64-float launch in other shapes, chosen per call by GD_SPMM_D64_FORM
-  //   8x2u2 / 8x2u4 : eight lanes x two float4 per row (eight neighbours per trip), 2 / 4 trips in flight
-  //   + "n" suffix  : the unweighted instantiation when val == NULL (no weight stream, no second crossbar read per trip)
-  if (d4 == 16 && addr32) {
+  // LAB (round 6): GD_SPMM_D64_FORM=16x1n runs the 64-float launch on the unweighted instantiation when
+  // val == NULL (no weight stream, no second crossbar read per trip)
+  if (d4 == 16 && addr32 && val == nullptr) {
     const char* form = getenv("GD_SPMM_D64_FORM");
-    if (form && *form) {
-      const bool nv = val == nullptr && strchr(form, 'n') != nullptr;
-#define GD_LAB_LAUNCH(LPR, VPL, UU, NV)                                                                             \
-  hipLaunchKernelGGL((spmm_persist_kernel<LPR, VPL, UU, true, true, NV>), grid, block, 0, s, it, n_items, xcd_bounds, col, val, x, \
-                     ldx, y, ldy, bias, self_coef, xs, scratch, d4, nnz)
-      if (!strncmp(form, "8x2u2", 5)) { if (nv) GD_LAB_LAUNCH(8, 2, 2, true); else GD_LAB_LAUNCH(8, 2, 2, false); return launched("spmm_persist"); }
-      if (!strncmp(form, "8x2u4", 5)) { if (nv) GD_LAB_LAUNCH(8, 2, 4, true); else GD_LAB_LAUNCH(8, 2, 4, false); return launched("spmm_persist"); }
-      if (!strncmp(form, "16x1", 4) && nv) { GD_LAB_LAUNCH(16, 1, 4, true); return launched("spmm_persist"); }
-#undef GD_LAB_LAUNCH
+    if (form && !strncmp(form, "16x1", 4) && strchr(form, 'n') != nullptr) {
+      hipLaunchKernelGGL((spmm_persist_kernel<16, 1, 4, true, true, true>), grid, block, 0, s, it, n_items, xcd_bounds, col, val, x,
+                         ldx, y, ldy, bias, self_coef, xs, scratch, d4, nnz);
+      return launched("spmm_persist");
     }
   }
   if (d4 <= 1) GD_ITEMS_CASE(1, 1);
@@ -692,6 +894,34 @@ extern "C" int gd_spmm_csr_onepass_f32(const int32_t* items, int32_t n_items, co
   GD_REQUIRE(aligned16(xs) && xs != y, GD_E_ALIGN, "gd_spmm_csr_onepass_f32: bad x_self");
   return launch_persist(items, n_items, col, val, x, ldx, y, ldy, bias, self_coef, xs, nullptr, d, nnz, x_rows,
                         xcd_bounds, (hipStream_t)stream);
+}
+
+extern "C" int gd_spmm_csr_onepass_wide_f32(const int32_t* items, int32_t n_items, const int32_t* col_tagged, const float* val,
+                                            const float* x, int64_t ldx, float* y, int64_t ldy, const float* bias,
+                                            float self_coef, const float* x_self, int32_t d, int32_t nnz, int32_t x_rows,
+                                            const int32_t* xcd_bounds, void* stream) {
+  using namespace gd;
+  GD_REQUIRE(col_tagged && x && y && xcd_bounds && (items || n_items == 0), GD_E_NULL, "gd_spmm_csr_onepass_wide_f32: null pointer");
+  GD_REQUIRE(n_items >= 0 && n_items % 4 == 0 && d == 64 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= d && ldy >= d, GD_E_DIM,
+             "gd_spmm_csr_onepass_wide_f32: d must be 64 (got %d) with 16-byte row strides, n_items a multiple of 4", d);
+  GD_REQUIRE(aligned16(x) && aligned16(y) && aligned16(items) && (!bias || aligned16(bias)), GD_E_ALIGN,
+             "gd_spmm_csr_onepass_wide_f32: unaligned pointer");
+  GD_REQUIRE(x != y, GD_E_DIM, "gd_spmm_csr_onepass_wide_f32: x and y must not alias");
+  GD_REQUIRE(x_rows > 0 && x_rows < (1 << 24) && ldx * 4 < (1 << 24) && ldy * 4 < (1 << 24) &&
+                 (int64_t)x_rows * ldx * 4 < (1ll << 32) && (int64_t)x_rows * ldy * 4 < (1ll << 32), GD_E_DIM,
+             "gd_spmm_csr_onepass_wide_f32: x and y must be smaller than 4 GiB with row ids and pitches below 2^24");
+  if (n_items == 0) return GD_OK;
+  const float* xs = x_self ? x_self : x;
+  GD_REQUIRE(aligned16(xs) && xs != y, GD_E_ALIGN, "gd_spmm_csr_onepass_wide_f32: bad x_self");
+  const char* e = getenv("GD_SPMM_GRID_CAP");               // tuning knob (blocks)
+  const int cap_env = e ? atoi(e) : 0;
+  const int cap = cap_env > 0 ? cap_env : GD_SPMM_WIDE_GRID_CAP;
+  int nblk = (n_items + 3) / 4;
+  if (nblk > cap) nblk = cap;
+  nblk = (nblk + 7) / 8 * 8;
+  hipLaunchKernelGGL(spmm_wide_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const int4*>(items), n_items,
+                     xcd_bounds, col_tagged, val, x, ldx, y, ldy, bias, self_coef, xs, nnz);
+  return launched("spmm_wide");
 }
 
 extern "C" int gd_spmm_csr_onepass_aux_f32(const int32_t* items, int32_t n_items, const int32_t* col, const int32_t* perm,

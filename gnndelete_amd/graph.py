@@ -17,6 +17,9 @@ from . import _lib
 
 
 CHUNK = 64   # in-edges per SpMM work item (one coalesced (col, val) fetch of a 64-lane wave)
+WIDE_ROWS = 16         # light rows per item of the wide 64-float form (SplitPlan.onepass_wide): the M of the matrix instruction
+WIDE_VISIT_COST = 48   # what a visit of that form costs its XCD beside its in-edges, in edges (onepass_wide; 24 / 48 / 64 / 96 measured in
+                       # the bench step: the two launches together 106.9 / 104.3 / 105.3 / 105.5 us, profiles/spmm_wide_ab.txt)
 
 
 class SplitPlan:
@@ -60,9 +63,12 @@ class SplitPlan:
         self._row_ids, self._row_start, self._row_end = ids, r_start, r_end
         self._row_deg, self._row_pieces = deg, pieces
         self._onepass = {}
+        self._nnz = int(rpl[-1])
+        self._wide_cols = {}         # index arrays with the wide form's row tags, per CSR index array (ops._wide_col)
         for d in (64, 128):          # the path's widths, ahead of any hipGraph capture (the tables are built lazily)
             self.xcd_bounds(d)
             self.onepass(d)
+        self.onepass_wide(64)
 
     def xcd_bounds(self, d):
         """Item range of each of the 8 XCDs for a width-d SpMM (int32 [9] on the device, None for small plans),
@@ -222,6 +228,123 @@ class SplitPlan:
         hit = (items, total, torch.tensor(bounds, dtype=torch.int32, device=dev))
         self._onepass[key] = hit
         self.n_multirow_items = n_multi
+        return hit
+
+    def onepass_wide(self, d=64, max_rows=None, visit_cost=None):
+        """(items int32 [n, 4], n, bounds int32 [9], tags int32 [nnz]) for gd_spmm_csr_onepass_wide_f32 (d = 64 only).  As
+        onepass: eight contiguous XCD ranges of equal cost, hub rows as 4-aligned GROUP quadruples (those above 4 pieces first in
+        their range, heaviest first), padding items {-1, 0, 0, -1}, every limit a multiple of 4.  The light rows travel up to
+        `max_rows` (<= 16) to an item {first row, start, end, -(16 + rows - 1)}: CONSECUTIVE rows - adjacent in the plan, in node
+        ids and in the CSR - with at most `chunk` in-edges together, packed greedily in row order (an item is closed by the first
+        row that does not fit, by a hub row, by a gap in the plan's rows).  tags[k] = the row of CSR entry k minus the first row
+        of its item (0 for hub rows and for rows outside the plan): the caller ORs it into bits 24 .. 27 of the index array.
+        The cost of an item to its XCD is its in-edges + `visit_cost` (once per item, not per row: descriptor, index fetch,
+        accumulator set-up and the 16-row epilogue are shared by the item's rows)."""
+        assert int(d) == 64, 'the wide form covers rows of exactly 64 floats'
+        max_rows = WIDE_ROWS if max_rows is None else int(max_rows)
+        a = WIDE_VISIT_COST if visit_cost is None else int(visit_cost)
+        assert 1 <= max_rows <= 16
+        key = ('wide', max_rows, a)
+        hit = self._onepass.get(key)
+        if hit is not None:
+            return hit
+        ids, r_start, r_end, deg, pieces = self._row_ids, self._row_start, self._row_end, self._row_deg, self._row_pieces
+        dev = ids.device
+        n = int(ids.numel())
+        chunk = CHUNK
+        tags = torch.zeros(self._nnz, dtype=torch.int32, device=dev)
+        if n == 0:
+            hit = (torch.zeros(0, 4, dtype=torch.int32, device=dev), 0, torch.zeros(9, dtype=torch.int32, device=dev), tags)
+            self._onepass[key] = hit
+            return hit
+        pos = torch.arange(n, device=dev)
+        pos1 = torch.arange(n + 1, device=dev)
+        light = pieces <= 1
+        # brk[p]: no item may run from row p - 1 into row p
+        brk = torch.ones(n + 1, dtype=torch.bool, device=dev)
+        if n > 1:
+            brk[1:n] = ~(light[1:] & light[:-1] & (ids[1:] == ids[:-1] + 1) & (r_start[1:] == r_end[:-1]))
+        cd = torch.cat([deg.new_zeros(1), torch.cumsum(deg, 0)])
+        fit = torch.searchsorted(cd, cd[:-1] + chunk, right=True) - 1          # largest q with deg[p .. q - 1] <= chunk
+        next_brk = torch.flip(torch.cummin(torch.flip(torch.where(brk, pos1, torch.full_like(pos1, n)), [0]), 0).values, [0])
+        nxt = torch.minimum(torch.minimum(pos + max_rows, fit), next_brk[1:])   # first row after the item that opens at p
+        nxt = torch.where(light, nxt, pos + 1)
+        # the rows that open an item = the orbit of `nxt` from every run start, marked by pointer doubling (the greedy rule
+        # itself is sequential)
+        opener = brk.clone()
+        jump = torch.cat([nxt, nxt.new_full((1,), n)])
+        for _ in range(max(1, int(n).bit_length())):
+            opener[jump[opener]] = True
+            jump = jump[jump]
+        opener = opener[:n]
+        first_pos = torch.cummax(torch.where(opener, pos, torch.zeros_like(pos)), 0).values
+        tag_row = pos - first_pos
+        sel = tag_row > 0
+        if bool(sel.any()):
+            rs, dg, tg = r_start[sel], deg[sel], tag_row[sel]
+            rep = torch.repeat_interleave(torch.arange(rs.numel(), device=dev), dg)
+            k_in = torch.arange(rep.numel(), device=dev) - (torch.cumsum(dg, 0) - dg)[rep]
+            tags[rs[rep] + k_in] = tg[rep].to(torch.int32)
+        # XCD ranges by cost, their limits moved up to the next row that opens an item
+        row_cost = deg + a * torch.where(light, opener.long(), pieces)
+        cost = torch.cumsum(row_cost.double(), 0)
+        cuts = torch.searchsorted(cost, cost[-1] * torch.arange(1, 8, device=dev, dtype=torch.float64) / 8)
+        next_open = torch.flip(torch.cummin(torch.flip(torch.where(opener, pos, torch.full_like(pos, n)), [0]), 0).values, [0])
+        next_open = torch.cat([next_open, next_open.new_full((1,), n)])
+        lim = [0] + [int(c) for c in next_open[torch.clamp(cuts, max=n)].tolist()] + [n]
+        for k in range(1, 9):
+            lim[k] = max(lim[k], lim[k - 1])
+        q4 = torch.arange(4, device=dev)
+
+        def members(hub):                                   # [len(hub) * 4, 4] group member items (as in onepass)
+            share = chunk * ((pieces[hub] + 3) // 4)
+            ms = r_start[hub][:, None] + share[:, None] * q4[None, :]
+            me = torch.minimum(ms + share[:, None], r_end[hub][:, None])
+            ms = torch.minimum(ms, me)
+            return torch.stack([ids[hub][:, None].expand(-1, 4), ms, me, torch.full_like(ms, -2)], 2).reshape(-1, 4)
+
+        pad_item = torch.tensor([-1, 0, 0, -1], device=dev)
+        parts, bounds, total = [], [0], 0
+        for k in range(8):
+            lo, hi = lim[k], lim[k + 1]
+            pk = pieces[lo:hi]
+            big = (pk > 4).nonzero().flatten() + lo
+            if big.numel():
+                big = big[torch.argsort(deg[big], descending=True, stable=True)]
+                parts.append(members(big))
+                total += 4 * int(big.numel())
+            rest = (pk <= 4).nonzero().flatten() + lo           # light rows and 2..4-piece hubs, in row order
+            if rest.numel():
+                is_hub = pieces[rest] > 1
+                op = opener[rest] & ~is_hub
+                opens = op.long()
+                light_run = torch.cumsum(opens, 0)
+                hub_pos = is_hub.nonzero().flatten()
+                prev = torch.cat([light_run.new_zeros(1), light_run[hub_pos][:-1]]) if hub_pos.numel() else light_run.new_zeros(0)
+                pad = (-(light_run[hub_pos] - prev)) % 4
+                slots = opens.clone()
+                slots[hub_pos] = 4 + pad
+                off = torch.cumsum(slots, 0) - slots
+                m = int(slots.sum())
+                blk = pad_item.expand(m, 4).clone()
+                o = rest[op]
+                if o.numel():
+                    blk[off[op]] = torch.stack([ids[o], r_start[o], r_end[nxt[o] - 1], -(16 + nxt[o] - o - 1)], 1)
+                if hub_pos.numel():
+                    first = off[hub_pos] + pad
+                    blk[(first[:, None] + q4[None, :]).reshape(-1)] = members(rest[hub_pos])
+                parts.append(blk)
+                total += m
+            tail = (-total) % 4
+            if tail:
+                parts.append(pad_item.expand(tail, 4))
+                total += tail
+            bounds.append(total)
+        items = torch.cat(parts, 0).to(torch.int32).contiguous() if parts else torch.zeros(0, 4, dtype=torch.int32, device=dev)
+        # the kernels' barrier invariant (include/gnndelete_hip.h): limits and group starts at multiples of 4
+        assert all(b % 4 == 0 for b in bounds) and total % 4 == 0, bounds
+        hit = (items, total, torch.tensor(bounds, dtype=torch.int32, device=dev), tags)
+        self._onepass[key] = hit
         return hit
 
     def scratch_flat(self, tag, n_floats, device):

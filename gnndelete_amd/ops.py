@@ -33,9 +33,10 @@ def _f32_rows(t):
 
 
 
-def _spmm_raw(rowptr, col, val, x, bias, self_coef, n_rows, plan=None, out=None, x_self=None):
+def _spmm_raw(rowptr, col, val, x, bias, self_coef, n_rows, plan=None, out=None, x_self=None, wide=True):
     """y = self_coef * x_self + A x + bias (x_self = x unless given; same row pitch).  With a SplitPlan
-    (and a float4-able width) the load-balanced kernel is used, otherwise the one-wave-per-row kernel."""
+    (and a float4-able width) the load-balanced kernel is used, otherwise the one-wave-per-row kernel.
+    wide=False keeps 64-float rows on the item kernel of gd_spmm_csr_onepass_f32 (a caller that needs its summation order)."""
     d = x.shape[1]
     if x_self is not None:
         assert plan is not None and x_self.stride(0) == x.stride(0) and x_self.shape[1] == d
@@ -43,6 +44,18 @@ def _spmm_raw(rowptr, col, val, x, bias, self_coef, n_rows, plan=None, out=None,
     if (plan is not None and d % 4 == 0 and d <= 1024 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
             and os.environ.get('GD_SPMM_TWO_LAUNCH') != '1'):
         # hub rows summed by the four waves of a block inside the same launch (no scratch rows, no fix-up kernel)
+        x_rows = max(int(x.shape[0]), int(y.shape[0]))
+        if (wide and d == 64 and x_rows < (1 << 24) and x.stride(0) * 4 < (1 << 24) and y.stride(0) * 4 < (1 << 24)
+                and x_rows * x.stride(0) * 4 < (1 << 32) and x_rows * y.stride(0) * 4 < (1 << 32)
+                and os.environ.get('GD_SPMM_MULTIROW') != '0' and not os.environ.get('GD_SPMM_D64_FORM')):
+            # 64-float rows: up to 16 light rows per item, summed by the fp32 matrix instruction (gd_spmm_csr_onepass_wide_f32);
+            # GD_SPMM_D64_FORM=pairs (any lab form) keeps the two-row items of the vector kernel (A/B), GD_SPMM_MULTIROW=0 its one-row items
+            items, n_items, bounds, tags = plan.onepass_wide(d)
+            check(_lib.lib().gd_spmm_csr_onepass_wide_f32(ptr(items), n_items, ptr(_wide_col(plan, col, tags)), ptr(val), ptr(x), x.stride(0),
+                                                          ptr(y), y.stride(0), ptr(bias), float(self_coef), ptr(x_self), d,
+                                                          int(col.shape[0]), x_rows, ptr(bounds), stream_ptr(x.device)),
+                  'gd_spmm_csr_onepass_wide_f32')
+            return y
         items, n_items, bounds = plan.onepass(d)
         check(_lib.lib().gd_spmm_csr_onepass_f32(ptr(items), n_items, ptr(col), ptr(val), ptr(x), x.stride(0), ptr(y),
                                                  y.stride(0), ptr(bias), float(self_coef), ptr(x_self), d, int(col.shape[0]),
@@ -126,6 +139,17 @@ def _lru_get(cache, key, capacity, build):
         hit = build()
     cache[key] = hit                                # (re-)insert as most recently used
     return hit
+
+
+def _wide_col(plan, col, tags):
+    """The CSR index array with the wide form's row tags in bits 24 .. 27 (col | tags << 24, tags from SplitPlan.onepass_wide),
+    built once per (plan, index array, tags) and kept on the plan; the entry holds `col` and `tags`, so their addresses cannot
+    be recycled."""
+    def build():
+        assert tags.shape[0] == col.shape[0], 'the plan was built for another CSR'
+        return (col | (tags << 24)).contiguous(), col, tags
+    hit = _lru_get(plan._wide_cols, (col.data_ptr(), int(col.shape[0]), col._version, tags.data_ptr()), 4, build)
+    return _note_constant(hit[0])
 
 
 _WT_CACHE = {}
@@ -613,7 +637,8 @@ def gat_backward_raw(graph, h, a_src, a_dst, rowmax, rowsum, dy, slope, plan=Non
     alpha_t = _ws_buf(bufs, 'alpha_t', (g.nnz,), dev)
     check(_lib.lib().gd_gat_transpose_edges_f32(ptr(g.rowptr_t), ptr(g.perm_t), ptr(ade), n, ptr(alpha_t),
                                                 ptr(da_src), stream_ptr(dev)), 'gd_gat_transpose_edges_f32')
-    dh = _spmm_raw(g.rowptr_t, g.col_t, alpha_t, dy, None, 0.0, n, pt, out=dh)
+    # (the item kernel gd_spmm_csr_onepass_aux_f32 sweeps with: this path is its reference, the same sums bit for bit)
+    dh = _spmm_raw(g.rowptr_t, g.col_t, alpha_t, dy, None, 0.0, n, pt, out=dh, wide=False)
     return dh, da_src, da_dst
 
 

@@ -48,7 +48,8 @@ extern "C" {
                                 the fused edge-probability step (entries added, none changed: the version stays);
                                 gd_rowfold_loss_f32 (+ _blocks), gd_rowfold_kld_scale_f32: the folded KLD / cosine row losses (entries added: the version stays);
                                 gd_edge_bce_f32, gd_col_sum_f32 (+ their _workspace queries): the fused backbone step (entries added: the version stays);
-                                gd_row_nll_f32 (+ its _workspace query): the fused node-classification step (entries added: the version stays) */
+                                gd_row_nll_f32 (+ its _workspace query): the fused node-classification step (entries added: the version stays);
+                                gd_spmm_csr_onepass_wide_f32: 64-float rows summed 16 rows per item on the matrix pipe (entry added: the version stays) */
 
 enum {
   GD_OK = 0,
@@ -164,6 +165,28 @@ int gd_spmm_csr_onepass_f32(const int32_t* items, int32_t n_items, const int32_t
                             const float* x, int64_t ldx, float* y, int64_t ldy, const float* bias, float self_coef,
                             const float* x_self, int32_t d, int32_t nnz, int32_t x_rows, const int32_t* xcd_bounds,
                             void* stream);
+
+/* WIDE form of gd_spmm_csr_onepass_f32 for rows of exactly 64 floats (same arithmetic, same call sites): an item is up to 16
+ * CONSECUTIVE light rows whose sums are formed by v_mfma_f32_16x16x4_f32 (Y[16 x 64] = S[16 x E] . X[E x 64], S = edge e's weight
+ * in the row of the output row the edge belongs to), one visit of a wave per item.
+ *   items [n_items, 4], n_items a multiple of 4:
+ *     {row, start, end, -(16 + nr - 1)}  nr <= 16 rows row .. row + nr - 1 whose in-edges [start, end) are adjacent in the CSR and
+ *                                        at most 64 together (rows without in-edges get bias + self term only);
+ *     {row, start, end, -2}              GROUP member of a row above 64 in-edges, as for gd_spmm_csr_onepass_f32: same trips,
+ *                                        same summation order, the same bits as that entry;
+ *     {-1, 0, 0, -1}                     padding.
+ *   col_tagged [nnz]: col[k] | local_row[k] << 24, local_row = the edge's row minus the first row of its item (0 for the
+ *                     edges of group members and of rows outside the plan).  SplitPlan.onepass_wide builds the tags.
+ *   d must be 64; x and y below 4 GiB with x_rows (an upper bound on the rows of x AND y) < 2^24 and pitches below 2^24 bytes.
+ *   xcd_bounds and its INVARIANT as for gd_spmm_csr_onepass_f32 (the kernel aborts on a range limit that is no multiple of 4).
+ * A row's sum is the fmaf chain over its own edges in item order, starting from the bias, + self_coef * x_self[row] at the end:
+ * bit-reproducible, equal to fp32 rounding to the other forms.  NON-FINITE INPUTS: the matrix instruction multiplies every
+ * gathered row into all 16 rows of the item (by 0 where the edge belongs to another row), so a source row that holds Inf or
+ * NaN poisons every row of the items that gather it, not only its true neighbours. */
+int gd_spmm_csr_onepass_wide_f32(const int32_t* items, int32_t n_items, const int32_t* col_tagged, const float* val,
+                                 const float* x, int64_t ldx, float* y, int64_t ldy, const float* bias, float self_coef,
+                                 const float* x_self, int32_t d, int32_t nnz, int32_t x_rows, const int32_t* xcd_bounds,
+                                 void* stream);
 
 /* gd_spmm_csr_onepass_f32 with the edge values read THROUGH a permutation from an interleaved (weight, addend) array kept in
  * another edge order (ABI 8): w[k] = aux[2 perm[k]], and aux_sum[row] = the sum of aux[2 perm[k] + 1] over the row's entries

@@ -14,9 +14,9 @@ NEXT = {
     'del1_loss_wgrad1': 'round 5: the previous iteration\'s conv2 input gradient (dt2[S1] W2, gated by the stored sign pattern) + Del-1 + folded layer-1 loss + the W_D1 weight gradient in ONE weight-stationary pass (was 59 + 83 + 40 us in three launches, 690 MB; now ~320 MB): instruction-bound (one wave per SIMD issues in order; 320 matrix instructions per 16-row unit and wave at the ~2.0 GHz the part sustains are 5.1 us of its ~6.9); both weights are LDS images (register-resident fragments leave no room for the third product); row-register rings, sched_group_barrier interleaving and a four-way column split all measured equal or slower (NOTES round 5)',
     'wgrad1': 'memory-side (366 MB algorithmic = 61 us at the fabric rate): 2 blocks per CU alternate fetch and MFMA phases; the output-stationary register form measured SLOWER (93 us, NOTES round 4) - it needs more rows in flight per CU, not fewer waves',
     't2': 'weight-stationary form with the two-buffer row selector and ReLU in the operand path: 52.1 -> 45 us; 193 MB at 4.3 TB/s',
-    'spmm2': 'latency / window-bound at 4.2-4.8 TB/s of traffic; round 6: eight lanes x two float4 per row (half the visits\' crossbar reads and address products) is 20-32 % SLOWER back to back and +6 % on the step - a row\'s two 128-byte lines asked for by different instructions; the weight stream is worth 3.7 / 1.6 us, all of it the load (profiles/r06_spmm_forms.txt, r06_spmm_forms_pmc.txt)',
+    'spmm2': 'wide form (gd_spmm_csr_onepass_wide_f32): up to 16 consecutive light rows per item, row sums by v_mfma_f32_16x16x4_f32 - 7.66 M vector instructions per launch against 17.3 M of the two-row vector form, the same 290 MB of fabric traffic; 67 -> 51 us in step, 5.6 TB/s of traffic; 45-48 us would be the d = 128 launch\'s rate; 7.4 k of the 40 k items are hub members, more are their alignment padding - not examined further (profiles/spmm_wide_ab.txt)',
     'del2_loss_bwd': 'weight-stationary form (round 4: W_D twice + the 64 x 64 dW sums in registers, 16-row units, no scratch): 62 -> 52 us; the three products of a unit are serial in one wave (loss arithmetic and the LDS transposition between them)',
-    'spmm2_t': 'as spmm2 (transposed CSR, S1 rows feed the next product)',
+    'spmm2_t': 'as spmm2 (transposed CSR, S1 rows feed the next product): 62 -> 52 us in step',
     'dh': 'weight-stationary form with the gate bits fetched a unit ahead: 47.2 -> 41 us; 148 MB at 3.6 TB/s',
     'tail': 'both split-K reductions + Adam + loss finalize in one launch (gd_step_tail_f32); launch-sized',
 }
