@@ -124,6 +124,14 @@ __device__ __forceinline__ void adam_update(float& p, float& m, float& v, float 
   p = p + (s.neg_step * m) / den;                           // param.addcdiv_(exp_avg, denom, -step_size)
 }
 
+// splitmix64 finaliser: the counter-based draws of sampler.hip (random walks) and negatives.hip (negative edges)
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {
+  z += 0x9e3779b97f4a7c15ull;
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+
 // Bijective remap of the hardware block id so that the blocks resident on one XCD (b % 8) cover a
 // contiguous range of logical block ids (placement is a speed assumption only, never correctness).
 __device__ __forceinline__ int xcd_contiguous_block(int b, int n_blocks) {

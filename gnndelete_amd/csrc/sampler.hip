@@ -7,13 +7,6 @@
 
 namespace gd {
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {     // splitmix64 finaliser
-  z += 0x9e3779b97f4a7c15ull;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-
 __global__ __launch_bounds__(256) void random_walk_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                           const int64_t* __restrict__ start, int32_t n_walks,
                                                           int32_t walk_length, uint64_t seed, int64_t* __restrict__ out) {

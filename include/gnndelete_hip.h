@@ -49,7 +49,8 @@ extern "C" {
                                 gd_rowfold_loss_f32 (+ _blocks), gd_rowfold_kld_scale_f32: the folded KLD / cosine row losses (entries added: the version stays);
                                 gd_edge_bce_f32, gd_col_sum_f32 (+ their _workspace queries): the fused backbone step (entries added: the version stays);
                                 gd_row_nll_f32 (+ its _workspace query): the fused node-classification step (entries added: the version stays);
-                                gd_spmm_csr_onepass_wide_f32: 64-float rows summed 16 rows per item on the matrix pipe (entry added: the version stays) */
+                                gd_spmm_csr_onepass_wide_f32: 64-float rows summed 16 rows per item on the matrix pipe (entry added: the version stays);
+                                gd_negative_edges: negative edges drawn on the device (entry added: the version stays) */
 
 enum {
   GD_OK = 0,
@@ -359,6 +360,26 @@ int gd_rgcn_wave_conv_f32(const int32_t* job_tile, int32_t n_tiles, int32_t tile
  * (rowptr / col), a node without out-edges keeps the walker.  The draw is a hash of (seed, w, s): reproducible. */
 int gd_random_walk(const int32_t* rowptr, const int32_t* col, int32_t n_nodes, const int64_t* start, int32_t n_walks,
                    int32_t walk_length, uint64_t seed, int64_t* out, void* stream);
+
+/* Negative edges on the device (csrc/negatives.hip): out[i], out[ld_out + i] for i < n_out is a node pair
+ * (a, b) with a != b and a * n_nodes + b NOT among pos_keys (framework/graph_utils.positive_edge_keys: sorted ascending,
+ * unique, int64; NULL with n_keys == 0: only self loops are excluded), uniform over all such pairs and independent per slot -
+ * negative_sampling's contract; duplicates among the negatives are possible, as in the host sampler.  A PURE FUNCTION of its
+ * arguments: slot i depends on (seed, *counter, i, pos_keys, n_nodes) only - not on n_out, the launch geometry or another
+ * slot; no generator state, no atomics, nothing to read back.  counter: a device scalar that is READ, never written (NULL =
+ * 0): a caller that advances it on the stream gets another draw per epoch without a word from the host.  The stream (mix64 = the splitmix64 finaliser, mulhi64 = the
+ * upper 64 bits of the 128-bit product):
+ *     base = mix64(seed ^ mix64(counter))
+ *     try t < 64:  c = mulhi64(mix64(base + 64 i + t), n_nodes^2);  accepted unless c / n == c % n or c is a key
+ *     after 64 rejected tries:  c <- (c + 1) mod n_nodes^2, at most n_nodes^2 times, until accepted
+ * mulhi64 maps 2^64 values onto n^2 cells: a cell's probability is off by at most n^2 / 2^64 relative (3e-9 at 235,868
+ * nodes).  Every loop is bounded: 2 (n_keys + n_nodes) <= n_nodes^2 is required (at most half of all pairs excluded;
+ * GD_E_DIM otherwise, as for n_nodes >= 2^31), so a try fails with probability <= 1/2, the probe is reached with
+ * probability <= 2^-64 per slot and ends because an allowed pair exists.  n_out == 0: GD_OK, no launch.  ld_out >= n_out;
+ * columns at and beyond n_out are not written.  One launch, one thread per slot, no runtime call besides it.
+ * gnndelete_amd/negatives.reference_draw restates the stream on the CPU bit for bit. */
+int gd_negative_edges(const int64_t* pos_keys, int64_t n_keys, int64_t n_nodes, uint64_t seed, const int64_t* counter,
+                      int64_t n_out, int64_t* out, int64_t ld_out, void* stream);
 
 /* The non-MSE row losses of the reference's loss zoo (framework/trainer/gnndelete_nodeemb.py:18-28), value per row
  * pair and gradient with respect to a, in one pass; rows of a / b optionally gathered through ia / ib (int64, NULL =
