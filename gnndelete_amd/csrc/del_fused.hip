@@ -311,12 +311,23 @@ __global__ __launch_bounds__(256, (NT == 2 && WG) ? 1 : 2) void del_loss_bwd_ker
 // SIMD).  Rows past the end are clamped to the last row and recompute it (identical stores); their loss / weight-gradient
 // contributions are zeroed.  Partial matrices: block b writes its sum to slot b and zeros to the slots b + grid, ... < n_part
 // (the reduction kernels count gd_rows_gemm_wgrad_blocks(n_sel) partials).
+//
+// FOLD (GCN / GIN chained step): P2 is not formed and wr2 not loaded.  Nothing reads dp there but the linear chain
+//     dt = A^T dp ;  dh[S1] = gate o (dt[S1] W_next)      (the transposed aggregation, then the NEXT iteration's chained Del-1 pass)
+// so dh[S1] = gate o ((A^T dz)[S1] (W_D^T W_next)): the kernel stores each row's dz where dp went (row `row`, pitch ld_dp, straight from
+// the accumulator layout) and the per-row [.., 64] x [64, 64] product becomes ONE [64, 64] x [64, 128] product on the weights,
+//     w_fold[i][n] = sum_c W_D[c][i] W_next[c][n]          (c ascending, one fmaf chain per output, no atomics)
+// written by the first blocks of this launch, one output per thread, from the W_D this launch's rows use (the tail launch steps
+// W_D afterwards).  128 instead of 192 matrix instructions per unit, 64 registers less; P1, the loss arithmetic, the tiles, the
+// deferred P3, the partial matrices and the loss partials are the same instructions in the same order.
 typedef float f32x4w __attribute__((ext_vector_type(4)));
-template <bool HAS_DZ>
+struct DelFold { const float* w_next; float* w_fold; };          // (FOLD) W_next [64, kFoldH] row-major; w_fold [64, kFoldH], 16-byte aligned
+constexpr int kFoldH = 128;
+template <bool HAS_DZ, bool FOLD = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void del_loss_bwd_ws_kernel(
     const float* __restrict__ p, int64_t ld_p, const int32_t* __restrict__ idx, int32_t n_sel, const float* __restrict__ w,
     DelLoss loss, float* __restrict__ dz, int64_t ld_dz, float* __restrict__ dp, int64_t ld_dp, float* __restrict__ wg_partials,
-    int32_t n_part) {
+    int32_t n_part, DelFold fold) {
   constexpr int D = 64, PT = 80;                                  // PT: pitch of the transposition tiles (rows 16 banks apart)
   extern __shared__ __attribute__((aligned(16))) float wl[];      // 4 waves x (2 tiles of 16 x PT), later 4 x D x D block sum
   __shared__ float lred[2][4];
@@ -334,18 +345,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   int32_t row_n = idx[slot_of(u_lo)], ls_n = loss.slot[slot_of(u_lo)];
   int32_t row_nn = idx[slot_of(u_lo + 1)], ls_nn = loss.slot[slot_of(u_lo + 1)];
   __builtin_amdgcn_sched_barrier(0);
-  float wr1[4][16], wr2[4][16];
+  float wr1[4][16], wr2[FOLD ? 1 : 4][16];
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int s_ = 0; s_ < 16; ++s_) wr1[t][s_] = w[(kq * 16 + s_) * D + 16 * t + r];
+  if (!FOLD) {
 #pragma unroll
-  for (int t2 = 0; t2 < 4; ++t2)
+    for (int t2 = 0; t2 < 4; ++t2)
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const float4 f = *reinterpret_cast<const float4*>(w + (16 * t2 + r) * D + 16 * t + 4 * kq);
-      wr2[t2][4 * t + 0] = f.x; wr2[t2][4 * t + 1] = f.y; wr2[t2][4 * t + 2] = f.z; wr2[t2][4 * t + 3] = f.w;
-    }
+      for (int t = 0; t < 4; ++t) {
+        const float4 f = *reinterpret_cast<const float4*>(w + (16 * t2 + r) * D + 16 * t + 4 * kq);
+        wr2[t2][4 * t + 0] = f.x; wr2[t2][4 * t + 1] = f.y; wr2[t2][4 * t + 2] = f.z; wr2[t2][4 * t + 3] = f.w;
+      }
+  }
   f32x4w gacc[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) gacc[i] = f32x4w{0.f, 0.f, 0.f, 0.f};
@@ -411,6 +424,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           }
       }
       __builtin_amdgcn_sched_barrier(0);
+      if (FOLD) {
+        // without P2 nothing behind the loss arithmetic covers the next unit's row fetch: the rows go to their tile and the next
+        // unit's are asked for as soon as P1 has read them, under P3 and the loss arithmetic (the tiles are free: the previous
+        // unit's views are in a_op / b_op)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<float4*>(tp + r * PT + kq * 16 + 4 * i) = x[i];
+        __builtin_amdgcn_sched_barrier(0);
+        fetch_rows(row_n);
+      }
       // ---- P3 of the PREVIOUS unit (operands in registers) - the scheduler interleaves it with what follows
       p3();
       // ---- loss gradient in the accumulator layout; p and dz into the transposition tiles
@@ -423,15 +445,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         sq = fmaf(d4.x, d4.x, sq); sq = fmaf(d4.y, d4.y, sq); sq = fmaf(d4.z, d4.z, sq); sq = fmaf(d4.w, d4.w, sq);
         g[t] = f32x4w{cf * d4.x, cf * d4.y, cf * d4.z, cf * d4.w};
         if (HAS_DZ) *reinterpret_cast<float4*>(dz + (int64_t)min(s_a, n_sel - 1) * ld_dz + 16 * t + 4 * kq) = make_float4(g[t][0], g[t][1], g[t][2], g[t][3]);
+        if (FOLD) *reinterpret_cast<float4*>(dp + (int64_t)row * ld_dp + 16 * t + 4 * kq) = make_float4(g[t][0], g[t][1], g[t][2], g[t][3]);
         *reinterpret_cast<float4*>(tz + r * PT + 16 * t + 4 * kq) = make_float4(livef * g[t][0], livef * g[t][1], livef * g[t][2], livef * g[t][3]);
       }
       sq *= livef;
       if (cn >= 0.f) ls0 = fmaf(cn, sq, ls0); else ls1 = fmaf(-cn, sq, ls1);
+      if (!FOLD) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) *reinterpret_cast<float4*>(tp + r * PT + kq * 16 + 4 * i) = x[i];
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<float4*>(tp + r * PT + kq * 16 + 4 * i) = x[i];
+      }
       __builtin_amdgcn_sched_barrier(0);
       fetch_targets(ls_n);                                         // the next unit's operands into the registers just consumed
-      fetch_rows(row_n);
+      if (!FOLD) fetch_rows(row_n);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the tiles are wave-private: DS operations execute in issue order
       __builtin_amdgcn_wave_barrier();
       // feature-major operands of this unit's P3: requested here, they arrive under P2
@@ -443,19 +468,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           b_op[sp][t] = tz[(4 * sp + kq) * PT + 16 * t + r];
         }
       __builtin_amdgcn_sched_barrier(0);
-      // ---- P2: dp = dz W_D^T
-      f32x4w dacc[4];
+      if (!FOLD) {
+        // ---- P2: dp = dz W_D^T
+        f32x4w dacc[4];
 #pragma unroll
-      for (int t = 0; t < 4; ++t)
+        for (int t = 0; t < 4; ++t)
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
+          for (int c = 0; c < 4; ++c)
 #pragma unroll
-          for (int t2 = 0; t2 < 4; ++t2) {
-            if (t == 0 && c == 0) dacc[t2] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr2[t2][0], g[0][0], f32x4w{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-            else dacc[t2] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr2[t2][4 * t + c], g[t][c], dacc[t2], 0, 0, 0);
-          }
-      __builtin_amdgcn_sched_barrier(0);
-      {
+            for (int t2 = 0; t2 < 4; ++t2) {
+              if (t == 0 && c == 0) dacc[t2] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr2[t2][0], g[0][0], f32x4w{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+              else dacc[t2] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr2[t2][4 * t + c], g[t][c], dacc[t2], 0, 0, 0);
+            }
+        __builtin_amdgcn_sched_barrier(0);
         float* orow = dp + (int64_t)row * ld_dp + 4 * kq;
 #pragma unroll
         for (int t2 = 0; t2 < 4; ++t2) *reinterpret_cast<float4*>(orow + 16 * t2) = make_float4(dacc[t2][0], dacc[t2][1], dacc[t2][2], dacc[t2][3]);
@@ -465,6 +490,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       __builtin_amdgcn_sched_barrier(0);
     }
     p3();                                                          // the last unit's weight-gradient product
+  }
+  if (FOLD) {
+    // ---- w_fold = W_D^T W_next on the first blocks, one output per thread and pass (a wave does its share when its units are
+    // done, in front of the block barrier it would wait at anyway); thread order = output order: W_next reads coalesce, the
+    // W_D element is one address per 128 outputs
+    const int nb = min((int)gridDim.x, D * kFoldH / 256);
+    if ((int)blockIdx.x < nb) {
+      for (int e = blockIdx.x * 256 + tid; e < D * kFoldH; e += nb * 256) {
+        const int i = e / kFoldH, n = e % kFoldH;
+        float acc = 0.f;
+#pragma unroll 16
+        for (int c = 0; c < D; ++c) acc = fmaf(w[c * D + i], fold.w_next[c * kFoldH + n], acc);
+        fold.w_fold[e] = acc;
+      }
+    }
   }
   // ---- block sum of the four waves' D x D sums (wave order), loss sums
   __syncthreads();
@@ -983,12 +1023,12 @@ static int del_loss_bwd_impl(const float* p, int64_t ld_p, const int32_t* idx, i
       static const hipError_t a1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&del_loss_bwd_ws_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsWs);
       if (a1 != hipSuccess) return fail(-(int)a1, "gd_del_loss_bwd_wgrad_f32: %s", hipGetErrorString(a1));
       hipLaunchKernelGGL((del_loss_bwd_ws_kernel<true>), dim3(grid_ws), dim3(256), kLdsWs, s, p, ld_p, idx, n_sel, w, loss, dz, ld_dz, dp, ld_dp,
-                         wgrad_partials, n_part);
+                         wgrad_partials, n_part, DelFold{nullptr, nullptr});
     } else {
       static const hipError_t a0 = hipFuncSetAttribute(reinterpret_cast<const void*>(&del_loss_bwd_ws_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsWs);
       if (a0 != hipSuccess) return fail(-(int)a0, "gd_del_loss_bwd_wgrad_f32: %s", hipGetErrorString(a0));
       hipLaunchKernelGGL((del_loss_bwd_ws_kernel<false>), dim3(grid_ws), dim3(256), kLdsWs, s, p, ld_p, idx, n_sel, w, loss, dz, ld_dz, dp, ld_dp,
-                         wgrad_partials, n_part);
+                         wgrad_partials, n_part, DelFold{nullptr, nullptr});
     }
     return launched("del_loss_bwd_ws");
   }
@@ -1043,6 +1083,39 @@ extern "C" int gd_del_loss_bwd_wgrad_parts_f32(const float* p, int64_t ld_p, con
   GD_REQUIRE(n_part > 0 || n_sel == 0, GD_E_DIM, "gd_del_loss_bwd_wgrad_parts_f32: n_part=%d", n_part);
   return del_loss_bwd_impl(p, ld_p, idx, n_sel, w, d, loss_slot, tm, coef, cnt_signed, dz, ld_dz, dp, ld_dp, loss_partials,
                            wgrad_partials, true, stream, n_part);
+}
+
+// the folded form exists where the weight-stationary kernel runs (d = 64, >= 65,536 rows, GD_DEL2_WS on) in front of a 128-wide W_next
+extern "C" int32_t gd_del_loss_fold_wgrad_covers(int32_t n_sel, int32_t d, int32_t h) {
+  static const bool ws_on = [] { const char* e = getenv("GD_DEL2_WS"); return !(e && atoi(e) == 0); }();
+  return ws_on && d == 64 && h == gd::kFoldH && n_sel >= 65536 ? 1 : 0;
+}
+
+extern "C" int gd_del_loss_fold_wgrad_parts_f32(const float* p, int64_t ld_p, const int32_t* idx, int32_t n_sel, const float* w, int32_t d,
+                                                const int32_t* loss_slot, const float* tm, const float* coef, const float* cnt_signed,
+                                                float* g, int64_t ld_g, const float* w_next, int32_t h, float* w_fold,
+                                                float* loss_partials, float* wgrad_partials, int32_t n_part, void* stream) {
+  using namespace gd;
+  const char* name = "gd_del_loss_fold_wgrad_parts_f32";
+  GD_REQUIRE(gd_del_loss_fold_wgrad_covers(n_sel, d, h), GD_E_DIM,
+             "%s: n_sel=%d, d=%d, h=%d is not covered (gd_del_loss_fold_wgrad_covers: d = 64, h = 128, >= 65,536 rows)", name, n_sel, d, h);
+  GD_REQUIRE(p && idx && w && loss_slot && tm && coef && cnt_signed && g && w_next && w_fold && loss_partials && wgrad_partials, GD_E_NULL,
+             "%s: null pointer", name);
+  GD_REQUIRE(ld_p >= d && ld_g >= d && ld_p % 4 == 0 && ld_g % 4 == 0, GD_E_DIM, "%s: bad row strides", name);
+  GD_REQUIRE(aligned16(p) && aligned16(tm) && aligned16(g) && aligned16(w) && aligned16(w_fold) && aligned16(wgrad_partials), GD_E_ALIGN,
+             "%s: unaligned", name);
+  GD_REQUIRE(p != g && w_fold != w && w_fold != w_next, GD_E_DIM, "%s: buffers must not alias", name);
+  const int n_all = gd_rows_gemm_wgrad_blocks(n_sel);
+  GD_REQUIRE(n_part <= n_all && n_part >= (ws_cu_count() < n_all ? ws_cu_count() : n_all), GD_E_DIM,
+             "%s: n_part=%d outside [gd_del_loss_bwd_wgrad_parts, gd_rows_gemm_wgrad_blocks = %d]", name, n_part, n_all);
+  const int grid_ws = ws_cu_count() < n_part ? ws_cu_count() : n_part;
+  constexpr int kLdsWs = 4 * 64 * 64 * 4;
+  static const hipError_t at = hipFuncSetAttribute(reinterpret_cast<const void*>(&del_loss_bwd_ws_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsWs);
+  if (at != hipSuccess) return fail(-(int)at, "%s: %s", name, hipGetErrorString(at));
+  const DelLoss loss{loss_slot, tm, coef, cnt_signed, loss_partials};
+  hipLaunchKernelGGL((del_loss_bwd_ws_kernel<false, true>), dim3(grid_ws), dim3(256), kLdsWs, (hipStream_t)stream, p, ld_p, idx, n_sel, w, loss,
+                     static_cast<float*>(nullptr), (int64_t)0, g, ld_g, wgrad_partials, n_part, DelFold{w_next, w_fold});
+  return launched("del_loss_fold_ws");
 }
 
 extern "C" int32_t gd_del1_loss_wgrad_covers(int32_t n_sel, int32_t d) {

@@ -29,6 +29,8 @@ backbone, loss, widths, row counts, the set relations between loss rows, Del row
 predicates - is gathered from the request into a StepFacts record.  KNOBS: read_knobs() reads every GD_* variable this module
 consults, once per construction.  FORMS: plan_step(facts, knobs) - a pure function of the two records, no tensors, no library
 calls - returns the StepForms the constructor then acts on in one pass (loss rows reordered, every buffer allocated once).
+One decision rides on top of the forms: plan_del2_fold(facts, forms, covers, enabled) - pure as well - says whether the chained
+GCN / GIN step folds W_D2 into conv2's weight (the Del-2 pass stores dz2 and W_D2^T W2 instead of forming dz2 W_D2^T per row).
 """
 import os
 import warnings
@@ -152,6 +154,22 @@ def plan_step(facts, k):
                  and not out1 and not out2 and closed)     # (loss rows outside the Del rows read conv outputs of rows outside S2)
     return StepForms(split1, split2, out1, out2, fuse_loss1, fuse_l2, tail, fuse_wg2, fuse_del1, chain1, out_pair, rows_only,
                      rows_only_asked and mode == 'rgcn', not k.no_gat_dots)
+
+
+def read_del2_fold(env=None):
+    """GD_DEL2_FOLD (default on; 0 = the unfolded step, for A/B runs).  Read once per construction like the Knobs; not a Knobs field:
+    plan_step does not read it and the recorded form tables spell the Knobs out."""
+    env = os.environ if env is None else env
+    return env.get('GD_DEL2_FOLD') != '0'
+
+
+def plan_del2_fold(facts, forms, covers, enabled=True):
+    """Does the fused Del-2 pass fold W_D2 into conv2's weight (gd_del_loss_fold_wgrad_parts_f32) instead of forming
+    dp2 = dz2 W_D2^T?  Pure.  Only where nothing reads dp2 but the linear chain dt2 = A^T dp2, dh[S1] = gate o (dt2[S1] W2) of the
+    chained GCN / GIN step - GAT's backward needs dp2 itself - where the weight-gradient partials come out of the same kernel,
+    and where every layer-2 loss row is a Del row: a loss row outside takes the identity, and W_D2^T W2 would apply W_D2 to it.
+    covers: gd_del_loss_fold_wgrad_covers(s2, o, h)."""
+    return bool(enabled and covers and forms.chain1 and facts.mode in ('gcn', 'gin') and forms.fuse_wg2 and not forms.out2)
 
 
 def _loss_coefficients(loss_type, alpha):
@@ -696,7 +714,13 @@ class NodeembEngine:
             self._gat_bufs = {'dh': torch.zeros(n, self.o, **f32), 'da_src': torch.zeros(n, **f32), 'da_dst': torch.zeros(n, **f32)}
         elif self._chain1:
             self._dt2_keep = torch.zeros(n, self.o, **f32)
-        self._gat_r1 = None                                            # (att_src W2, att_dst W2): constants of the frozen conv2
+        # _fold2 (plan_del2_fold): the fused Del-2 pass leaves dz2 where dp2 went and W_D2^T W2 in _w2fold; the transposed
+        # aggregation gathers dz2 instead (same buffer, rows and width) and the NEXT iteration's chained Del-1 pass takes _w2fold
+        # for W2: (A^T dz2)[S1] (W_D2^T W2) = (A^T dp2)[S1] W2 without the per-row product.  Carried across iterations like
+        # _dt2_keep; zeros at the start (the first chained pass multiplies it by the zero dt2)
+        self._fold2 = plan_del2_fold(self.facts, self.forms, lib.gd_del_loss_fold_wgrad_covers(self.s2, self.o, self.h), read_del2_fold())
+        self._w2fold = torch.zeros(self.o, self.h, **f32) if self._fold2 else None
+        self._gat_r1 = None                                           # (att_src W2, att_dst W2): constants of the frozen conv2
         if self._mode == 'gat':
             w2_ = conv2.lin_src.weight.detach()
             self._gat_r1 = ((conv2.att_src.detach().reshape(1, -1) @ w2_).reshape(-1).float().contiguous(),
@@ -1114,6 +1138,11 @@ class NodeembEngine:
             if self._user_wd2 is not None:          # padded class dimension: the caller's W_D2 is the top-left block
                 self._user_wd2.data.copy_(self.wd2.data[:self._o_true, :self._o_true])
 
+    def _conv2_weight(self):
+        """conv2's [O, H] weight of the GCN / GIN step (frozen)."""
+        c2 = self.model.conv2
+        return (c2.lin if self._mode == 'gcn' else c2.nn).weight.detach()
+
     def _del1_fused(self, g_add):
         """Del-1 forward (+ sign bits) + folded layer-1 loss + the W_D1 weight gradient's partial sums in one kernel
         (csrc/del_fused.hip, del1_loss_wgrad_ws_kernel); the tail launch reduces them and steps Adam."""
@@ -1125,7 +1154,9 @@ class NodeembEngine:
                 w_next, dt = c2.lin_src.weight.detach(), self._gat_bufs['dh']
                 rank1 = (ptr(self._gat_bufs['da_src']), ptr(self._gat_r1[0]), ptr(self._gat_bufs['da_dst']), ptr(self._gat_r1[1]))
             else:
-                w_next, dt = (c2.lin if self._mode == 'gcn' else c2.nn).weight.detach(), self._dt2_keep
+                w_next, dt = self._conv2_weight(), self._dt2_keep
+                if self._fold2:                # dt = A^T dz2 of the previous iteration; its W_D2^T W2 came out of that Del-2 pass
+                    w_next = self._w2fold
                 rank1 = (None, None, None, None)
             check(_lib.lib().gd_del1_chain_loss_wgrad_f32(
                 ptr(self.pre1), self.pre1.stride(0), ptr(self.idx1), self.s1, ptr(self.wd1), self.h, ptr(self.z1), self.z1.stride(0),
@@ -1141,7 +1172,15 @@ class NodeembEngine:
 
     def _del2_fused(self):
         """Del-2 forward + folded layer-2 loss + Del-2 input gradient (+ the W_D2 weight gradient's partial sums) in one
-        kernel (csrc/del_fused.hip)."""
+        kernel (csrc/del_fused.hip).  _fold2: dz2 instead of the input gradient, and W_D2^T W2 for the next chained Del-1 pass."""
+        if self._fold2:
+            w2 = self._conv2_weight()
+            check(_lib.lib().gd_del_loss_fold_wgrad_parts_f32(
+                ptr(self.p2), self.p2.stride(0), ptr(self.idx2), self.s2, ptr(self.wd2), self.o, ptr(self._slot2),
+                ptr(self.t2.tm), ptr(self.t2.coef), ptr(self._cnt_signed2), ptr(self.dz2), self.dz2.stride(0), ptr(w2), self.h,
+                ptr(self._w2fold), ptr(self._lp2), ptr(self.ws2), self._lp2_blocks, stream_ptr(self.x.device)),
+                'gd_del_loss_fold_wgrad_parts_f32')
+            return
         if self._fuse_wg2:
             check(_lib.lib().gd_del_loss_bwd_wgrad_parts_f32(
                 ptr(self.p2), self.p2.stride(0), ptr(self.idx2), self.s2, ptr(self.wd2), self.o, ptr(self._slot2),
@@ -1221,6 +1260,8 @@ class NodeembEngine:
         if self._chain1:                                    # carried from one iteration to the next in the chained form
             state += [self.z1_pos] + ([self._dt2_keep] if self._dt2_keep is not None else
                                       [self._gat_bufs[k] for k in ('dh', 'da_src', 'da_dst')])
+        if self._fold2:
+            state.append(self._w2fold)
         state.append(self._arrive)      # step_tail's check-in counter: a launch that did not finish must not leave it non-zero
         if self._user_wd2 is not None:                      # the caller's W_D2 behind a padded class dimension
             state.append(self._user_wd2.data)

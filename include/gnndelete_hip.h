@@ -583,6 +583,19 @@ int gd_del_loss_bwd_wgrad_parts_f32(const float* p, int64_t ld_p, const int32_t*
                                     const int32_t* loss_slot, const float* tm, const float* coef, const float* cnt_signed,
                                     float* dz, int64_t ld_dz, float* dp, int64_t ld_dp, float* loss_partials,
                                     float* wgrad_partials, int32_t n_part, void* stream);
+/* The same pass with the Del input gradient FOLDED into the next weight (the GCN / GIN chained step, where nothing reads dp but
+ * dt = A^T dp and then (dt W_next) in gd_del1_chain_loss_wgrad_f32 - both linear, the gate behind them): no dp = dz W_D^T; instead
+ *     g[idx[s],:] = dz[s,:]   (the rows dp would have gone to, pitch ld_g; other rows untouched)
+ *     w_fold[64, h] = W_D^T @ w_next[64, h]   (row-major, contiguous, 16-byte aligned; one fmaf chain over c = 0..63 per output,
+ *                                              from the W_D this launch reads: bit-reproducible)
+ * so that (A^T g) w_fold = (A^T dp) w_next up to rounding.  loss_partials and wgrad_partials: the bits of
+ * gd_del_loss_bwd_wgrad_parts_f32 on the same input, n_part as there.  gd_del_loss_fold_wgrad_covers(n_sel, d, h): 1 for d = 64,
+ * h = 128 and >= 65,536 rows (the weight-stationary kernel's range; GD_DEL2_WS=0 turns it off); the entry refuses everything else. */
+int32_t gd_del_loss_fold_wgrad_covers(int32_t n_sel, int32_t d, int32_t h);
+int gd_del_loss_fold_wgrad_parts_f32(const float* p, int64_t ld_p, const int32_t* idx, int32_t n_sel, const float* w, int32_t d,
+                                     const int32_t* loss_slot, const float* tm, const float* coef, const float* cnt_signed,
+                                     float* g, int64_t ld_g, const float* w_next, int32_t h, float* w_fold,
+                                     float* loss_partials, float* wgrad_partials, int32_t n_part, void* stream);
 
 /* (ABI 8) FIRST-layer Del operator at d = 128, its folded loss and its weight gradient in one pass over the S_Df rows - what
  * gd_rows_gemm_signs_f32 followed by gd_rows_gemm_wgrad_loss_f32 (dw = NULL) compute in two (p read once, z only written):

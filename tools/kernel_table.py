@@ -15,7 +15,7 @@ NEXT = {
     'wgrad1': 'memory-side (366 MB algorithmic = 61 us at the fabric rate): 2 blocks per CU alternate fetch and MFMA phases; the output-stationary register form measured SLOWER (93 us, NOTES round 4) - it needs more rows in flight per CU, not fewer waves',
     't2': 'weight-stationary form with the two-buffer row selector and ReLU in the operand path: 52.1 -> 45 us; 193 MB at 4.3 TB/s',
     'spmm2': 'wide form (gd_spmm_csr_onepass_wide_f32): up to 16 consecutive light rows per item, row sums by v_mfma_f32_16x16x4_f32 - 7.66 M vector instructions per launch against 17.3 M of the two-row vector form, the same 290 MB of fabric traffic; 67 -> 51 us in step, 5.6 TB/s of traffic; 45-48 us would be the d = 128 launch\'s rate; 7.4 k of the 40 k items are hub members, more are their alignment padding - not examined further (profiles/spmm_wide_ab.txt)',
-    'del2_loss_bwd': 'weight-stationary form (round 4: W_D twice + the 64 x 64 dW sums in registers, 16-row units, no scratch): 62 -> 52 us; the three products of a unit are serial in one wave (loss arithmetic and the LDS transposition between them)',
+    'del2_loss_bwd': 'weight-stationary form (round 4: 16-row units, the 64 x 64 dW sums in registers, no scratch), folded: the kernel `del_loss_bwd_ws_kernel<false, true>` stores dz2 where dp2 went and writes W_D2^T W2 for the next chained Del-1 pass instead of forming dz2 W_D2^T per row - 128 instead of 192 matrix instructions per unit, W_D held once; the next unit\'s rows are asked for right behind P1 (P2 used to cover that fetch): 52.4 -> 44.8 us in step (profiles/del2_fold_ab.txt; GD_DEL2_FOLD=0 = the unfolded form). The GF figure is bench.py\'s label of the stage and still counts P2\'s flops (6 s2 o^2; the folded pass does 4 s2 o^2), so fraction and TF are a third too high',
     'spmm2_t': 'as spmm2 (transposed CSR, S1 rows feed the next product): 62 -> 52 us in step',
     'dh': 'weight-stationary form with the gate bits fetched a unit ahead: 47.2 -> 41 us; 148 MB at 3.6 TB/s',
     'tail': 'both split-K reductions + Adam + loss finalize in one launch (gd_step_tail_f32); launch-sized',
