@@ -115,6 +115,10 @@ PROTOTYPES = {
     'gd_edgeprob_dec_f32': (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _i64, _p, _i64, _i64, _f32, _p, _p, _p, _p, _p, _p, _p]),
     'gd_edge_incidence_workspace': (_i64, [_i64, _i64]),
     'gd_edge_incidence': (ctypes.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _i64, _p]),
+    'gd_edge_incidence_fixed_bytes': (_i64, [_i64, _i64]),
+    'gd_edge_incidence_fixed': (ctypes.c_int, [_p, _p, _i64, _i64, _p, _i64, _p, _i64, _p]),
+    'gd_edge_incidence_update_workspace': (_i64, [_i64, _i64]),
+    'gd_edge_incidence_update': (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _i64, _p]),
     'gd_rows_add_f32': (ctypes.c_int, [_p, _i64, _i64, _p, _i32, _p, _i64, _f32, _i32, _p]),
     'gd_edgeprob_record_f32': (ctypes.c_int, [_p, _p, _f32, _f32, _p, _i32, _p, _p]),
     'gd_edge_bce_workspace': (_i64, [_i64, _i32]),

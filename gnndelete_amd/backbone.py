@@ -29,6 +29,7 @@ import torch
 from . import _lib, ops
 from ._lib import check, ptr, stream_ptr
 from .capture import capture_iterations
+from .negatives import DeviceNegatives
 
 
 def padded_class_width(C):
@@ -157,9 +158,11 @@ def col_sum(x, row_w=None, gate=None, gated=None, out=None, ws=None):
     return out
 
 
-class BackboneEngine:
+class BackboneEngine(DeviceNegatives):
     """One backbone-training request: model (GCN / GAT of framework/models/backbones.py, every parameter is stepped in place),
-    node features, the message-passing edges, the positive decoded edges (int64 [2, P]) and the number of negatives per epoch."""
+    node features, the message-passing edges, the positive decoded edges (int64 [2, P]) and the number of negatives per epoch.
+    step(neg) takes the epoch's negatives from the caller; after enable_device_negatives(pos_keys, seed), step_device() draws
+    them on the device."""
 
     def __init__(self, model, x, mp_edges, pos_edges, n_neg, lr, betas, eps, history=4096, use_graph=True):
         self._setup(model, x, mp_edges, lr, betas, eps, history, use_graph)
@@ -169,6 +172,7 @@ class BackboneEngine:
         # the decoded edges [pos | neg]: the positive half is fixed, the negatives' half is rewritten by step()
         P, n_neg = self.P, self.n_neg = int(pos_edges.shape[1]), int(n_neg)
         M = self.M = P + n_neg
+        self._n_fixed = P
         if M < 1:
             raise ValueError('BackboneEngine: no decoded edges (upstream\'s mean over nothing is NaN)')
         self.dec = torch.zeros(2, M, **i64)
@@ -389,6 +393,14 @@ class BackboneEngine:
         self._mark('incidence')
         self._run_iteration()
 
+    def step_device(self):
+        """One epoch on negatives drawn on the device (enable_device_negatives first): the draw into the negatives' half of the
+        decoded edges, the incidence list merged from the positives' image, the iteration as in step(), the draw counter + 1 -
+        stream launches and a graph replay, no host read, no allocation."""
+        self._draw_and_merge()
+        self._run_iteration()
+        self._next_draw()
+
     def _run_iteration(self):
         if not self._use_graph:
             self._iteration()
@@ -474,3 +486,6 @@ class NodeClassifierEngine(BackboneEngine):
         """One epoch: one graph replay."""
         self._mark('start')
         self._run_iteration()
+
+    def enable_device_negatives(self, pos_keys, seed, counter=0):
+        raise TypeError('NodeClassifierEngine: the node-classification step decodes no edges and draws no negatives')

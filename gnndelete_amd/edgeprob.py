@@ -19,6 +19,7 @@ import torch
 from . import _lib, ops
 from ._lib import check, ptr, stream_ptr
 from .capture import capture_iterations
+from .negatives import DeviceNegatives
 
 
 def fused_edgeprob_unsupported(model, args, optimizer):
@@ -61,6 +62,32 @@ def edge_incidence(e0, e1, n):
     return inc_ptr, other[:2 * m2], src_edge[:2 * m2]
 
 
+def edge_incidence_image(e0, e1, n_fixed, n):
+    """gd_edge_incidence_fixed: the image (an opaque int64 tensor) of the first n_fixed edges of (e0, e1) over n nodes."""
+    e0, e1 = e0.contiguous().long(), e1.contiguous().long()
+    dev, L = e0.device, _lib.lib()
+    image = torch.empty(L.gd_edge_incidence_fixed_bytes(n, n_fixed) // 8 + 1, dtype=torch.int64, device=dev)
+    ws = torch.empty(L.gd_edge_incidence_update_workspace(n, n_fixed) // 8 + 1, dtype=torch.int64, device=dev)
+    check(L.gd_edge_incidence_fixed(ptr(e0), ptr(e1), n_fixed, n, ptr(image), 8 * image.numel(), ptr(ws), 8 * ws.numel(),
+                                    stream_ptr(dev)), 'gd_edge_incidence_fixed')
+    return image
+
+
+def edge_incidence_update(image, e0, e1, n_fixed, n):
+    """gd_edge_incidence_update: edge_incidence(e0, e1, n)'s three arrays from the image of the first n_fixed edges and the
+    edges [n_fixed, M) of (e0, e1)."""
+    e0, e1 = e0.contiguous().long(), e1.contiguous().long()
+    m2 = int(e0.shape[0])
+    dev, L = e0.device, _lib.lib()
+    inc_ptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    other = torch.empty(max(2 * m2, 1), dtype=torch.int32, device=dev)
+    src_edge = torch.empty(max(2 * m2, 1), dtype=torch.int32, device=dev)
+    ws = torch.empty(L.gd_edge_incidence_update_workspace(n, m2) // 8 + 1, dtype=torch.int64, device=dev)
+    check(L.gd_edge_incidence_update(ptr(image), ptr(e0), ptr(e1), n_fixed, m2, n, ptr(inc_ptr), ptr(other), ptr(src_edge), ptr(ws),
+                                     8 * ws.numel(), stream_ptr(dev)), 'gd_edge_incidence_update')
+    return inc_ptr, other[:2 * m2], src_edge[:2 * m2]
+
+
 def rows_add_(dz, nodes, src, scale):
     """dz[nodes[i], :] += scale * src[i, :] in place for sorted unique int32 rows (gd_rows_add_f32)."""
     n_s = int(nodes.shape[0])
@@ -69,10 +96,11 @@ def rows_add_(dz, nodes, src, scale):
     return dz
 
 
-class EdgeprobEngine:
+class EdgeprobEngine(DeviceNegatives):
     """One edge-probability request: model (GCNDelete / GATDelete, its Del weights are stepped in place), node features,
     the S_Df edges of the forward, the Df edges, and the pair term's (nodes int32, dense target, pair count) as
-    GNNDeleteTrainer builds them (target None / n_pairs 0: no pair term, loss_l = 0)."""
+    GNNDeleteTrainer builds them (target None / n_pairs 0: no pair term, loss_l = 0).  step(neg) takes the epoch's negatives
+    from the caller; after enable_device_negatives(pos_keys, seed), step_device() draws them on the device."""
 
     def __init__(self, model, x, e_sdf, df_edges, nodes32, target, n_pairs, lr, betas, eps, history=4096, use_graph=True):
         from .graph import graph_for
@@ -105,7 +133,7 @@ class EdgeprobEngine:
         self.s1, self.s2 = int(self.idx1.shape[0]), int(self.idx2.shape[0])
         self.wd1, self.wd2 = model.deletion1.deletion_weight, model.deletion2.deletion_weight
         # the decoded edges [pos | neg]: the Df half is fixed, the negatives' half is rewritten by step()
-        m = self.m = int(df_edges.shape[1])
+        m = self.m = self._n_fixed = int(df_edges.shape[1])
         if m < 1:
             raise ValueError('EdgeprobEngine: no Df edges (upstream\'s MSE of nothing is NaN)')
         i64 = dict(dtype=torch.int64, device=dev)
@@ -234,6 +262,22 @@ class EdgeprobEngine:
         for st in self.adam:
             st['steps'] += 1
         self.steps_done += 1
+
+    def step_device(self):
+        """One epoch on negatives drawn on the device (enable_device_negatives first): the draw into the negatives' half of the
+        decoded edges, the incidence list merged from the Df edges' image, the iteration as in step(), the draw counter + 1 -
+        stream launches and a graph replay, no host read, no allocation."""
+        self._draw_and_merge()
+        if not self._use_graph:
+            self._iteration()
+        else:
+            if self._graph is None:
+                self._capture()
+            self._graph.replay()
+        for st in self.adam:
+            st['steps'] += 1
+        self.steps_done += 1
+        self._next_draw()
 
     def last_losses(self):
         """(train_loss, loss_l, loss_r) of the latest step: one blocking host read."""

@@ -107,6 +107,23 @@ class Trainer:
         pos_keys = graph_utils.positive_edge_keys(edges, num_nodes)
         return lambda n_neg: graph_utils.negative_sampling_cached(pos_keys, num_nodes, n_neg)
 
+    def _device_negative_keys(self, args, fused, sampler, edges, num_nodes, flag='fused_backbone'):
+        """--device_negatives: the sorted keys of `edges` (the pairs the host draw excludes) when this run draws its negatives
+        on the device, else None and the host draw stays; with the flag, trainer_log['negatives'] says 'device' or why not.
+        fused: whether the fused step (--`flag`) applies; sampler: the trainer module's negative_sampling (the tests' seam)."""
+        if not getattr(args, 'device_negatives', False):
+            return None
+        from ...negatives import device_negatives_fallback
+        from .. import graph_utils
+        replaced = sampler is not graph_utils.negative_sampling
+        keys = graph_utils.positive_edge_keys(edges, num_nodes) if fused and not replaced else None
+        reason = device_negatives_fallback(flag, fused, replaced, None if keys is None else keys.numel(), num_nodes)
+        self.trainer_log['negatives'] = 'device' if reason is None else reason
+        if reason is not None:
+            print(f'--device_negatives: {reason}; drawing the negatives on the host', flush=True)
+            return None
+        return keys
+
     def train_minibatch(self, model, data, optimizer, args):
         """base.py:144-227: per GraphSAINT batch, BCE link prediction on the batch's edges against one negative per
         edge; best-validation-loss checkpoint."""
@@ -162,14 +179,21 @@ class Trainer:
         fused = self._fused_backbone_applies(model, optimizer, args)
         engine = None
         draw = self._cached_negative_draw(negative_sampling, edges, data.num_nodes) if fused else None
+        device_keys = self._device_negative_keys(args, fused, negative_sampling, edges, data.num_nodes)
         for epoch in range(args.epochs):
             model.train()
-            neg = draw(n_neg) if draw is not None else negative_sampling(edges, data.num_nodes, n_neg)
-            if fused:
+            if device_keys is not None:             # --device_negatives: no host work between the epochs' replays
+                if engine is None:
+                    engine = self._backbone_engine(model, data, edges.contiguous(), n_neg, optimizer, args)
+                    engine.enable_device_negatives(device_keys, args.random_seed)
+                engine.step_device()
+            elif fused:
+                neg = draw(n_neg) if draw is not None else negative_sampling(edges, data.num_nodes, n_neg)
                 if engine is None:                  # (sized by the first draw: the loop takes whatever count the sampler gives)
                     engine = self._backbone_engine(model, data, edges.contiguous(), int(neg.shape[1]), optimizer, args)
                 engine.step(neg)
             else:
+                neg = negative_sampling(edges, data.num_nodes, n_neg)
                 z = model(data.x, edges)
                 logits = model.decode(z, edges, neg)
                 loss = F.binary_cross_entropy_with_logits(logits, get_link_labels(edges, neg))

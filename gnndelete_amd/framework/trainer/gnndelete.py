@@ -172,11 +172,16 @@ class GNNDeleteTrainer(Trainer):
             else:
                 print(f'--fused_edgeprob: {reason}; running the autograd loop', flush=True)
             self.trainer_log['edgeprob_step'] = 'fused' if engine is not None else 'autograd'
+        device_keys = self._device_negative_keys(args, engine is not None, negative_sampling, edges, data.num_nodes, 'fused_edgeprob')
+        if device_keys is not None:                 # --device_negatives: no host work between the epochs' replays
+            engine.enable_device_negatives(device_keys, args.random_seed)
         best_metric = 0
         for epoch in range(args.epochs):
             model.train()
             start = time.time()
-            if engine is not None:
+            if device_keys is not None:
+                engine.step_device()
+            elif engine is not None:
                 engine.step(draw())
             else:
                 z = model(data.x, e_sdf)

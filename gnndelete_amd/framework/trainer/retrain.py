@@ -46,16 +46,25 @@ class RetrainTrainer(Trainer):
                 steps.append({'Epoch': ep, 'train_loss': hist[ep - engine.steps_done]})
                 wandb_log(steps[-1])
             return steps[-1]
+        device_keys = self._device_negative_keys(args, fused, negative_sampling, edges, data.num_nodes)
         for epoch in range(args.epochs):
             model.train()
-            if draw is not None:
+            if device_keys is not None:
+                pass                                # --device_negatives: no host work between the epochs' replays
+            elif draw is not None:
                 neg = draw(n_neg)
             else:
                 neg = negative_sampling(edge_index=edges, num_nodes=data.num_nodes, num_neg_samples=n_neg)
             if fused:
                 if engine is None:                  # (sized by the first draw: the loop takes whatever count the sampler gives)
-                    engine = self._backbone_engine(model, data, edges, int(neg.shape[1]), optimizer, args)
-                engine.step(neg)
+                    engine = self._backbone_engine(model, data, edges, n_neg if device_keys is not None else int(neg.shape[1]),
+                                                   optimizer, args)
+                    if device_keys is not None:
+                        engine.enable_device_negatives(device_keys, args.random_seed)
+                if device_keys is not None:
+                    engine.step_device()
+                else:
+                    engine.step(neg)
                 if (epoch + 1) % self.args.valid_freq == 0:
                     step_log = read_steps()
                     engine.export_adam_state(optimizer)         # (a checkpoint below carries the optimizer's state)

@@ -69,6 +69,7 @@ EXTRA_FLAGS = [
     ('fused_minibatch', None, False, 'with --minibatch: run each GraphSAINT batch on the fused HIP batch step (GCN / GAT, MSE losses) instead of the autograd loop'),
     ('fused_edgeprob', None, False, 'with --unlearning_model gnndelete: run the full-graph edge-probability step on the fused HIP engine (GCN / GAT, one Adam) instead of the autograd loop'),
     ('fused_backbone', None, False, 'train_gnn.py and --unlearning_model retrain: run the full-batch link-prediction training step on the fused HIP engine (GCN / GAT, one plain Adam) instead of the autograd loop; train_node.py: the node-classification (NLL) training step likewise, up to 256 classes'),
+    ('device_negatives', None, False, 'where --fused_backbone / --fused_edgeprob applies: draw each epoch\'s negatives on the device (seeded by --random_seed; a different random stream than the host sampler) and merge them into the decoder\'s incidence list there, no host work between epochs'),
     ('fused_row_losses', None, False, 'with --loss_fct kld_mean / kld_sum / cosine_mean / cosine_sum: run the full-batch node-embedding step on the fused HIP engine (folded row losses) instead of the autograd loop'),
     ('no_fused_step', None, False, 'use the autograd path even where the fused hipGraph step applies'),
     ('no_layer1_cache', None, False, 'recompute the frozen layer-1 output every epoch as upstream does (identical results)'),

@@ -4,8 +4,10 @@ The fused steps that take fresh negatives every epoch (BackboneEngine, EdgeprobE
 of 1.2 x the count, a copy, a searchsorted and a cat per epoch, and the GPU waiting for them (profiles/backbone_fused.json).
 gd_negative_edges draws the same kind of pairs - negative_sampling's contract: int64 [2, n_out], no positive edge, no self
 loop, uniform over the rest, duplicates possible - as a pure function of (seed, counter, slot, pos_keys, n_nodes): one launch,
-no generator state, and a counter that may live on the device.  This module is the kernel's wrapper and its CPU restatement;
-no engine or trainer calls it yet.
+no generator state, and a counter that may live on the device.  This module is the kernel's wrapper, its CPU restatement and
+what the two engines share of step_device() (DeviceNegatives: the draw straight into the decoded list, the incidence list
+merged from a fixed image by gd_edge_incidence_update, the counter bump - plain launches around the captured iteration);
+--device_negatives switches the trainers to it.
 
 The stream, which reference_draw below restates in numpy uint64 bit for bit (it is the kernel's test oracle):
 
@@ -129,3 +131,59 @@ def device_negative_edges(pos_keys, n_nodes, seed, counter, n_out, out=None):
                                            ptr(counter), n_out, ptr(out), out.stride(0) if n_out else 0, stream_ptr(dev)),
               'gd_negative_edges')
     return out[:, :n_out]
+
+
+def device_negatives_fallback(flag, fused, sampler_replaced, n_keys=None, n_nodes=None):
+    """Why a trainer keeps the host draw under --device_negatives (one line), or None when the device draws.  flag: the fused
+    flag's name; fused: whether the fused step applies to this run; sampler_replaced: the trainer module's negative_sampling
+    is not graph_utils.negative_sampling (the tests' seam); n_keys / n_nodes: the excluded pairs and the graph's size."""
+    if not fused:
+        return f'--{flag} is missing or fell back'
+    if sampler_replaced:
+        return 'negative_sampling has been replaced'
+    return device_negatives_unsupported(n_keys, n_nodes)
+
+
+class DeviceNegatives:
+    """What BackboneEngine and EdgeprobEngine share of step_device().  The host class has dec (int64 [2, n_edges], the
+    first _n_fixed columns fixed), n, dev, inc_ptr / other / src_edge and _mark()."""
+    _neg = None
+
+    def enable_device_negatives(self, pos_keys, seed, counter=0):
+        """Negatives from gd_negative_edges from now on (step_device): pos_keys = graph_utils.positive_edge_keys over the edges
+        the draw excludes; slot i of epoch k is reference_draw(pos_keys, n, seed, counter + k, n_neg)[:, i].  Raises ValueError
+        before any launch where the kernel does not take the graph; builds the image of the fixed half of the decoded list."""
+        from . import _lib
+        from ._lib import check, ptr, stream_ptr
+        n_keys = 0 if pos_keys is None else int(pos_keys.numel())
+        reason = device_negatives_unsupported(n_keys, self.n)
+        if reason is not None:
+            raise ValueError(f'enable_device_negatives: {reason}')
+        L, dev, n = _lib.lib(), self.dev, self.n
+        fixed, total = self._n_fixed, int(self.dec.shape[1])
+        keys = None if not n_keys else pos_keys.to(device=dev, dtype=torch.int64).contiguous()
+        image = torch.empty(L.gd_edge_incidence_fixed_bytes(n, fixed) // 8 + 1, dtype=torch.int64, device=dev)
+        ws = torch.empty(L.gd_edge_incidence_update_workspace(n, total) // 8 + 1, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            check(L.gd_edge_incidence_fixed(ptr(self.dec[0]), ptr(self.dec[1]), fixed, n, ptr(image), 8 * image.numel(), ptr(ws),
+                                            8 * ws.numel(), stream_ptr(dev)), 'gd_edge_incidence_fixed')
+        self._neg = {'keys': keys, 'seed': int(seed), 'counter': torch.tensor([int(counter)], dtype=torch.int64, device=dev),
+                     'image': image, 'ws': ws}
+
+    def _draw_and_merge(self):
+        """This epoch's negatives into dec[:, fixed:] and the incidence list of the whole of dec: launches only."""
+        from . import _lib
+        from ._lib import check, ptr, stream_ptr
+        if self._neg is None:
+            raise RuntimeError('step_device: call enable_device_negatives(pos_keys, seed) first')
+        st, fixed, total = self._neg, self._n_fixed, int(self.dec.shape[1])
+        self._mark('start')
+        device_negative_edges(st['keys'], self.n, st['seed'], st['counter'], total - fixed, out=self.dec[:, fixed:])
+        self._mark('draw')
+        check(_lib.lib().gd_edge_incidence_update(ptr(st['image']), ptr(self.dec[0]), ptr(self.dec[1]), fixed, total, self.n,
+                                                  ptr(self.inc_ptr), ptr(self.other), ptr(self.src_edge), ptr(st['ws']),
+                                                  8 * st['ws'].numel(), stream_ptr(self.dev)), 'gd_edge_incidence_update')
+        self._mark('incidence')
+
+    def _next_draw(self):
+        self._neg['counter'].add_(1)        # in place, on the stream: the next epoch's draw without a word from the host

@@ -50,7 +50,9 @@ extern "C" {
                                 gd_edge_bce_f32, gd_col_sum_f32 (+ their _workspace queries): the fused backbone step (entries added: the version stays);
                                 gd_row_nll_f32 (+ its _workspace query): the fused node-classification step (entries added: the version stays);
                                 gd_spmm_csr_onepass_wide_f32: 64-float rows summed 16 rows per item on the matrix pipe (entry added: the version stays);
-                                gd_negative_edges: negative edges drawn on the device (entry added: the version stays) */
+                                gd_negative_edges: negative edges drawn on the device (entry added: the version stays);
+                                gd_edge_incidence_fixed, gd_edge_incidence_update (+ their size queries): the incidence list when only
+                                the tail of the decoded edges changes (entries added: the version stays) */
 
 enum {
   GD_OK = 0,
@@ -780,6 +782,35 @@ int gd_edgeprob_dec_f32(const float* z, int64_t ld_z, int64_t n_nodes, int32_t d
 int64_t gd_edge_incidence_workspace(int64_t n_nodes, int64_t n_edges);
 int gd_edge_incidence(const int64_t* e0, const int64_t* e1, int64_t n_edges, int64_t n_nodes, int64_t* inc_ptr,
                       int32_t* other, int32_t* src_edge, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The same list when only the tail of the decoded edges changes between calls (csrc/incidence.hip): the edges are
+ * [fixed | variable], n_fixed of them fixed (the positives), the rest rewritten every epoch (the negatives).  Node v's list in
+ * the stable order is [fixed, e0 = v | variable, e0 = v | fixed, e1 = v | variable, e1 = v], each part by ascending edge index.
+ *
+ * gd_edge_incidence_fixed, once per request: from the edges [0, n_fixed) of (e0, e1), an IMAGE of gd_edge_incidence_fixed_bytes
+ * (n_nodes, n_fixed) bytes - per node the fixed entries in stable order (source entries first), how many of them are source
+ * entries, and the node of every entry.  workspace: gd_edge_incidence_update_workspace(n_nodes, n_fixed) BYTES.
+ *
+ * gd_edge_incidence_update, once per epoch: e0 / e1 are the WHOLE list of n_edges edges, of which only [n_fixed, n_edges) is
+ * read; the image (of the same n_nodes and n_fixed, READ ONLY here) stands for the rest.  Writes exactly what gd_edge_incidence
+ * (e0, e1, n_edges, n_nodes, ...) writes, bit for bit and the same bits every call: per epoch two integer counts per variable
+ * edge, a scan over the nodes (three launches: sums per 1,024-node tile, one block over the tile sums, the tiles again), a
+ * streaming copy of the fixed entries to their shifted places and a rank of each variable entry among its node's variable
+ * entries of the same side (a list of L such entries costs L^2: slow when every variable edge meets one node, still exact).
+ * gd_edge_incidence's contract in both halves: an edge with an endpoint outside [0, n_nodes) has no entries, the tail of other /
+ * src_edge beyond inc_ptr[n_nodes] is not written; n_edges == n_fixed and n_fixed == 0 are legal.  workspace:
+ * gd_edge_incidence_update_workspace(n_nodes, n_edges) BYTES; image and workspace 8-byte aligned (GD_E_ALIGN).
+ *
+ * Both are kernel launches on the stream and nothing else (no memset, no copy; the counters are zeroed by the first launch of
+ * every call, so a count is never added to what an earlier call left), no block waits on another, every loop is bounded by an
+ * argument, and every store is guarded by 2 n_edges. */
+int64_t gd_edge_incidence_fixed_bytes(int64_t n_nodes, int64_t n_fixed);
+int gd_edge_incidence_fixed(const int64_t* e0, const int64_t* e1, int64_t n_fixed, int64_t n_nodes, void* image, int64_t image_bytes,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int64_t gd_edge_incidence_update_workspace(int64_t n_nodes, int64_t n_edges);
+int gd_edge_incidence_update(const void* image, const int64_t* e0, const int64_t* e1, int64_t n_fixed, int64_t n_edges,
+                             int64_t n_nodes, int64_t* inc_ptr, int32_t* other, int32_t* src_edge, void* workspace,
+                             int64_t workspace_bytes, void* stream);
 
 /* dz[nodes[i], :] += scale * src[i, :] for i < n_s: the compact [n_s, d] pair-term gradient of
  * gd_pairs_sigmoid_mse_f32 joins a dense [n_rows, d] gradient.  nodes must be UNIQUE (plain vector loads and stores, no

@@ -1,6 +1,8 @@
 """Per-epoch time of link-prediction backbone training: today's autograd loop (Trainer.train_fullbatch /
-RetrainTrainer.train_fullbatch without --fused_backbone) against the fused HIP step (gnndelete_amd.backbone), in one process,
-the autograd loop first.
+RetrainTrainer.train_fullbatch without --fused_backbone) against the fused HIP step (gnndelete_amd.backbone) on the host draw
+and on the device draw (--device_negatives: step_device, the draw and the incidence merge inside the timed region), in one
+process on three copies of the model, the three legs' regions alternating.  --parent_records embeds the fused legs of records
+the PARENT commit's script wrote on the same box: the device leg is to be compared with those, not with this tree's host leg alone.
 
 synth-dblp and synth-collab, GCN (in -> 128 -> 64): original training (every training edge) and retrain at --df in
 --df_size 5 (the retained edges only).  Every epoch draws its negatives inside the timed region, as the trainers do (the loop:
@@ -68,26 +70,21 @@ def measure(graph, gnn, request, epochs):
     start = [p.detach().clone() for p in model.parameters()]
     res = {'graph': graph, 'gnn': gnn, 'request': request, 'nodes': n, 'features': int(x.shape[1]), 'edges': int(edges.shape[1]),
            'negatives': n_neg, 'epochs_per_region': epochs, 'regions': REGIONS}
-    # ---- today's loop (the flag off)
-    opt = torch.optim.Adam(model.parameters(), lr=lr)
+    # ---- three legs on three copies of the model, from the same starting parameters: today's loop (the flag off), the fused
+    # step on the host draw (--fused_backbone), the fused step on the device draw (--fused_backbone --device_negatives)
+    import copy
+    auto_model, dev_model = copy.deepcopy(model), copy.deepcopy(model)
+    opt = torch.optim.Adam(auto_model.parameters(), lr=lr)
     last = {}
 
     def autograd_epoch():
         neg = GU.negative_sampling(edges, n, n_neg)
-        z = model(x, edges)
-        loss = F.binary_cross_entropy_with_logits(model.decode(z, edges, neg), get_link_labels(edges, neg))
+        z = auto_model(x, edges)
+        loss = F.binary_cross_entropy_with_logits(auto_model.decode(z, edges, neg), get_link_labels(edges, neg))
         loss.backward()
         opt.step()
         opt.zero_grad()
         last['loss'] = loss
-    region(autograd_epoch, lambda: last['loss'].item(), epochs)
-    t_auto = [region(autograd_epoch, lambda: last['loss'].item(), epochs) for _ in range(REGIONS)]
-    # RetrainTrainer reads the loss on every epoch
-    t_auto_read = [region(lambda: (autograd_epoch(), last['loss'].item()), lambda: None, epochs) for _ in range(REGIONS)]
-    # ---- the fused step (the flag on), from the same starting parameters
-    with torch.no_grad():
-        for p, s in zip(model.parameters(), start):
-            p.copy_(s)
     t0 = time.perf_counter()
     pos_keys = GU.positive_edge_keys(edges, n)
     eng = BackboneEngine(model, x, edges, edges, n_neg, lr, (0.9, 0.999), 1e-8, history=4096)
@@ -96,8 +93,23 @@ def measure(graph, gnn, request, epochs):
     torch.cuda.synchronize()
     res['fused_setup_ms'] = round(1e3 * (time.perf_counter() - t0), 1)
     fused_epoch = lambda: eng.step(draw())
-    region(fused_epoch, eng.last_loss, epochs)
-    t_fused = [region(fused_epoch, eng.last_loss, epochs) for _ in range(REGIONS)]
+    t0 = time.perf_counter()
+    dev = BackboneEngine(dev_model, x, edges, edges, n_neg, lr, (0.9, 0.999), 1e-8, history=4096)
+    dev.enable_device_negatives(GU.positive_edge_keys(edges, n), 42)
+    dev.step_device()                                 # (captures the graph)
+    torch.cuda.synchronize()
+    res['device_setup_ms'] = round(1e3 * (time.perf_counter() - t0), 1)
+    legs = (('autograd', autograd_epoch, lambda: last['loss'].item()), ('fused', fused_epoch, eng.last_loss),
+            ('device', dev.step_device, dev.last_loss))
+    times = {name: [] for name, _, _ in legs}
+    for name, epoch, read in legs:                    # warm-up regions
+        region(epoch, read, epochs)
+    for _ in range(REGIONS):                          # the legs alternate: a drift of the box meets all three alike
+        for name, epoch, read in legs:
+            times[name].append(region(epoch, read, epochs))
+    t_auto, t_fused, t_dev = times['autograd'], times['fused'], times['device']
+    # RetrainTrainer reads the loss on every epoch
+    t_auto_read = [region(lambda: (autograd_epoch(), last['loss'].item()), lambda: None, epochs) for _ in range(REGIONS)]
     # ---- where the fused epoch's time goes: the negative draw on its own, the eager step's stages by events
     t_draw = [region(draw, lambda: None, epochs) for _ in range(REGIONS)]
     t_draw_unique = [region(lambda: GU.negative_sampling(edges, n, n_neg), lambda: None, epochs) for _ in range(REGIONS)]
@@ -126,10 +138,42 @@ def measure(graph, gnn, request, epochs):
     res['ratio'] = round(res['autograd_ms_per_epoch'] / res['fused_ms_per_epoch'], 2)
     res['ratio_host_clock'] = round(res['autograd_host_clock_ms_per_epoch'] / res['fused_host_clock_ms_per_epoch'], 2)
     res['fused_eager_stage_ms'] = {k: round(float(np.median([s[k] for s in stages])), 4) for k in stages[0]}
+    # the device leg: its regions, and the eager step's stages with the draw and the incidence merge inside
+    res['device_ms_per_epoch'], res['device_host_clock_ms_per_epoch'] = ms(t_dev, 0), ms(t_dev, 1)
+    res['device_regions_ms'] = [round(1e3 * v[0], 4) for v in t_dev]
+    res['fused_over_device'] = round(res['fused_ms_per_epoch'] / res['device_ms_per_epoch'], 2)
+    with torch.no_grad():
+        for p, s in zip(dev_model.parameters(), start):
+            p.copy_(s)
+    eager = BackboneEngine(dev_model, x, edges, edges, n_neg, lr, (0.9, 0.999), 1e-8, use_graph=False)
+    eager.enable_device_negatives(pos_keys, 42)
+    stages = []
+    for k in range(2 * epochs):
+        eager.events = []
+        eager.step_device()
+        torch.cuda.synchronize()
+        ev = eager.events
+        if k >= epochs:
+            stages.append({b[0]: a[1].elapsed_time(b[1]) for a, b in zip(ev[:-1], ev[1:])})
+    res['device_eager_stage_ms'] = {k: round(float(np.median([s[k] for s in stages])), 4) for k in stages[0]}
+    res['final_loss_device'] = dev.last_loss()
     res['first_product'], res['first_weight_gradient'] = eng.fwd1, eng.wgrad1
     res['final_loss_fused'] = eng.last_loss()
     res['kernel_source_stamp'] = _lib.build_stamp()[0]
     return res
+
+
+def parent_legs(paths):
+    """The fused legs of the parent commit's records (one list entry per record and run)."""
+    out = []
+    for path in paths:
+        with open(path) as f:
+            rec = json.load(f)
+        for run in rec['runs']:
+            out.append({'record': os.path.basename(path), 'kernel_source_stamp': rec['kernel_source_stamp'],
+                        **{k: run[k] for k in ('graph', 'gnn', 'request', 'fused_ms_per_epoch', 'fused_host_clock_ms_per_epoch',
+                                               'fused_regions_ms', 'fused_eager_stage_ms', 'negative_draw_ms_per_epoch')}})
+    return out
 
 
 def main():
@@ -139,6 +183,8 @@ def main():
     ap.add_argument('--gnn', nargs='+', default=['gcn'])
     ap.add_argument('--requests', nargs='+', default=['original', 'retrain'])
     ap.add_argument('--epochs', type=int, default=30)
+    ap.add_argument('--parent_records', nargs='*', default=[],
+                    help='records this script wrote at the PARENT commit on the same box: their fused legs go into --out as "parent"')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('backbone_fused.py measures on the GPU: none found')
@@ -151,7 +197,8 @@ def main():
                 if a.out:
                     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
                     with open(a.out, 'w') as f:
-                        json.dump({'kernel_source_stamp': runs[0]['kernel_source_stamp'], 'runs': runs}, f, indent=1)
+                        json.dump({'kernel_source_stamp': runs[0]['kernel_source_stamp'], 'runs': runs,
+                                   **({'parent': parent_legs(a.parent_records)} if a.parent_records else {})}, f, indent=1)
                         f.write('\n')
 
 

@@ -6,11 +6,14 @@ synth-dblp, GCN and GAT (in -> 128 -> 64), --df out --df_size 2.5.  Every epoch 
 region, as the trainer does (the loop: negative_sampling; the engine: negative_sampling_cached).  Per path: 50 warm-up
 epochs, then five regions of 50 epochs, each closed by the read of the last loss (the trainer's host read on a validation
 epoch); the figure is the median region / 50.  The stage split of the fused step comes from CUDA events around the
-eager (uncaptured) step; the negative draw is timed on its own (host clock, device synchronised).  Prints one JSON line
-per backbone and writes them all to --out as one JSON object.
+eager (uncaptured) step; the negative draw is timed on its own (host clock, device synchronised).  A third leg is the
+fused step on the device draw (--device_negatives: step_device, the draw and the incidence merge inside the timed region) on
+a copy of the model; its regions alternate with the host-draw leg's.  Prints one JSON line per backbone and writes them all
+to --out as one JSON object.
 
     python tools/experiments/edgeprob_fused.py [--out FILE] [--gnn gcn gat]"""
 import argparse
+import copy
 import json
 import os
 import sys
@@ -105,7 +108,17 @@ def measure(gnn):
     res['fused_setup_ms'] = round(1e3 * (time.perf_counter() - t0), 1)
     fused_epoch = lambda: eng.step(draw())
     region(fused_epoch, eng.last_losses, EPOCHS)
-    t_fused = [region(fused_epoch, eng.last_losses, EPOCHS) for _ in range(REGIONS)]
+    # ---- the fused step on the device draw (--device_negatives), on a copy of the model; its regions alternate with the host leg's
+    dev_model = copy.deepcopy(model)
+    dev = EdgeprobEngine(dev_model, data.x, req.e_sdf, req.df_edges, req.nodes32, req.target, req.n_pairs, lr, (0.9, 0.999), 1e-8,
+                         history=4096)
+    dev.enable_device_negatives(pos_keys, 42)
+    dev.step_device()                                 # (captures the graph)
+    region(dev.step_device, dev.last_losses, EPOCHS)
+    t_fused, t_dev = [], []
+    for _ in range(REGIONS):
+        t_fused.append(region(fused_epoch, eng.last_losses, EPOCHS))
+        t_dev.append(region(dev.step_device, dev.last_losses, EPOCHS))
     # ---- where the fused epoch's time goes: the eager negative draw on its own, the eager step's stages by events
     t_draw = [region(draw, lambda: None, EPOCHS) for _ in range(REGIONS)]
     t_draw_unique = [region(lambda: GU.negative_sampling(edge_index=req.edges, num_nodes=data.num_nodes, num_neg_samples=req.m),
@@ -130,6 +143,21 @@ def measure(gnn):
     res['negative_draw_share_of_fused_epoch'] = round(res['negative_draw_ms_per_epoch'] / res['fused_ms_per_epoch'], 3)
     res['negative_draw_with_unique_ms_per_epoch'] = ms(t_draw_unique)
     res['fused_eager_stage_ms'] = {k: round(float(np.median([s[k] for s in stages])), 4) for k in stages[0]}
+    res['device_ms_per_epoch'] = ms(t_dev)
+    res['device_regions_ms'] = [round(1e3 * v, 4) for v in t_dev]
+    res['fused_over_device'] = round(res['fused_ms_per_epoch'] / res['device_ms_per_epoch'], 2)
+    eager = EdgeprobEngine(dev_model, data.x, req.e_sdf, req.df_edges, req.nodes32, req.target, req.n_pairs, lr, (0.9, 0.999), 1e-8,
+                           use_graph=False)
+    eager.enable_device_negatives(pos_keys, 42)
+    stages = []
+    for k in range(2 * EPOCHS):
+        eager.events = []
+        eager.step_device()
+        torch.cuda.synchronize()
+        ev = eager.events
+        if k >= EPOCHS:
+            stages.append({b[0]: a[1].elapsed_time(b[1]) for a, b in zip(ev[:-1], ev[1:])})
+    res['device_eager_stage_ms'] = {k: round(float(np.median([s[k] for s in stages])), 4) for k in stages[0]}
     res['kernel_source_stamp'] = _lib.build_stamp()[0]
     return res
 
