@@ -121,6 +121,9 @@ PROTOTYPES = {
     'gd_edge_incidence_update': (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _i64, _p]),
     'gd_rows_add_f32': (ctypes.c_int, [_p, _i64, _i64, _p, _i32, _p, _i64, _f32, _i32, _p]),
     'gd_edgeprob_record_f32': (ctypes.c_int, [_p, _p, _f32, _f32, _p, _i32, _p, _p]),
+    'gd_edgeprob_batch_loss_workspace': (_i64, [_i64, _i64, _i32]),
+    'gd_edgeprob_batch_loss_f32': (ctypes.c_int, [_p, _i64, _i64, _p, _i64, _i64, _i32, _p, _i64, _p, _i64, _i64, _p, _p, _i64, _f32, _f32,
+                                                  _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p]),
     'gd_edge_bce_workspace': (_i64, [_i64, _i32]),
     'gd_edge_bce_f32': (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _i64, _i64, _p, _i64, _i64, _f32, _p, _p, _p, _p, _p, _p, _p]),
     'gd_col_sum_workspace': (_i64, [_i64, _i32]),

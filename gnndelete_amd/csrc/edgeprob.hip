@@ -6,7 +6,10 @@
 //   gd_edge_incidence     the node-major incidence list gd_edge_dot_bwd_f32 walks, in the order a stable sort of
 //                         cat(e0, e1) gives (what ops._EdgeDot.backward builds with torch.sort + searchsorted);
 //   gd_rows_add_f32       dz[nodes[i], :] += s * src[i, :] for sorted unique rows (the compact pair-term gradient);
-//   gd_edgeprob_record_f32  the epoch's three losses into a device history ring.
+//   gd_edgeprob_record_f32  the epoch's three losses into a device history ring;
+//   gd_edgeprob_batch_loss_f32  the loss stage of a GraphSAINT batch of the mini-batch loop (:364-400): both terms over the
+//                         decoded list [Df edges | negatives | the batch's S_Df edges with src < dst], their logit
+//                         gradients, the incidence list and the gradients in incidence order.
 //
 // Everything that is summed is summed in a fixed order (per-block partials, then one thread in block order); the only
 // atomics are integer counters whose final values do not depend on arrival order.
@@ -194,6 +197,138 @@ static inline int dec_blocks(int64_t m, int lpr) {
   return (int)((m + per_block - 1) / per_block);
 }
 
+// ---- the loss stage of a GraphSAINT batch (gd_edgeprob_batch_loss_f32).  Items t < k are the DEC pairs (Df edge t against
+// negative t, both dots in z), items t >= k the candidates c = t - k (the same edge in z and in z_ori).
+constexpr int kBatchLossMaxBlocks = 2048;
+
+// this lane's share of <tab[i0], tab[i1]>; 0 when an endpoint is outside [0, rows) (nothing outside tab is read)
+template <int LPR>
+__device__ __forceinline__ float pair_dot_part(const float* __restrict__ tab, int64_t ld, int64_t rows, int64_t i0, int64_t i1,
+                                               int32_t d4, int li) {
+  float acc = 0.f;
+  if (i0 >= 0 && i0 < rows && i1 >= 0 && i1 < rows) {
+    const float4* x = reinterpret_cast<const float4*>(tab + i0 * ld);
+    const float4* y = reinterpret_cast<const float4*>(tab + i1 * ld);
+    for (int vec = li; vec < d4; vec += LPR) {
+      const float4 xv = x[vec], yv = y[vec];
+      acc = fmaf(xv.x, yv.x, acc); acc = fmaf(xv.y, yv.y, acc); acc = fmaf(xv.z, yv.z, acc); acc = fmaf(xv.w, yv.w, acc);
+    }
+  }
+  return acc;
+}
+
+// One lane group per item, the grid walks the k + n_cand items in strides.  Writes the decoded list [pos | neg | candidates]
+// ((-1, -1) for a candidate that does not count), the raw difference of every item (0 where nothing counts) and one
+// (sum of squares DEC, sum of squares locality, counted candidates) partial per block.
+template <int LPR>
+__global__ __launch_bounds__(256) void edgeprob_batch_dots_kernel(
+    const float* __restrict__ z, int64_t ld_z, int64_t n, const float* __restrict__ z_ori, int64_t ld_o, int64_t n_o, int32_t d4,
+    const int64_t* __restrict__ pos, int64_t ld_pos, const int64_t* __restrict__ neg, int64_t ld_neg, int64_t k,
+    const int64_t* __restrict__ cand_src, const int64_t* __restrict__ cand_dst, int64_t n_cand, int64_t* __restrict__ dec,
+    int64_t ld_dec, float* __restrict__ raw, float* __restrict__ part_e, float* __restrict__ part_l,
+    int32_t* __restrict__ part_n) {
+  constexpr int G = kWave / LPR;
+  __shared__ float red_e[4], red_l[4];
+  __shared__ int32_t red_n[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane / LPR, li = lane % LPR;
+  const int64_t total = k + n_cand, per_grid = (int64_t)gridDim.x * 4 * G;
+  float sq_e = 0.f, sq_l = 0.f;
+  int32_t counted = 0;
+  for (int64_t base = (int64_t)blockIdx.x * 4 * G; base < total; base += per_grid) {
+    const int64_t t = base + wave * G + g;
+    int64_t s0 = -1, s1 = -1;
+    float a = 0.f, b = 0.f;
+    bool counts = false;
+    if (t < k) {
+      const int64_t p0 = pos[t], p1 = pos[ld_pos + t], q0 = neg[t], q1 = neg[ld_neg + t];
+      a = pair_dot_part<LPR>(z, ld_z, n, p0, p1, d4, li);
+      b = pair_dot_part<LPR>(z, ld_z, n, q0, q1, d4, li);
+      if (li == 0) {
+        dec[t] = p0; dec[ld_dec + t] = p1;
+        dec[k + t] = q0; dec[ld_dec + k + t] = q1;
+      }
+    } else if (t < total) {
+      const int64_t c0 = cand_src[t - k], c1 = cand_dst[t - k];
+      counts = c0 < c1;
+      if (counts) {
+        s0 = c0; s1 = c1;
+        a = pair_dot_part<LPR>(z, ld_z, n, c0, c1, d4, li);
+        b = pair_dot_part<LPR>(z_ori, ld_o, n_o, c0, c1, d4, li);
+      }
+      if (li == 0) { dec[k + t] = s0; dec[ld_dec + k + t] = s1; }
+    }
+#pragma unroll
+    for (int off = 1; off < LPR; off <<= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); }
+    if (t < total && li == 0) {
+      const float diff = a - b;               // (0 for a candidate that does not count)
+      raw[t] = diff;
+      if (t < k) sq_e = fmaf(diff, diff, sq_e);
+      else if (counts) { sq_l = fmaf(diff, diff, sq_l); ++counted; }
+    }
+  }
+  sq_e = wave_sum(sq_e);
+  sq_l = wave_sum(sq_l);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) counted += __shfl_xor(counted, off);
+  if (lane == 0) { red_e[wave] = sq_e; red_l[wave] = sq_l; red_n[wave] = counted; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    part_e[blockIdx.x] = (red_e[0] + red_e[1]) + (red_e[2] + red_e[3]);
+    part_l[blockIdx.x] = (red_l[0] + red_l[1]) + (red_l[2] + red_l[3]);
+    part_n[blockIdx.x] = (red_n[0] + red_n[1]) + (red_n[2] + red_n[3]);
+  }
+}
+
+// Every block adds the integer partial counts (n_l; order cannot matter), scales the raw differences into w in decoded
+// order and, when asked to, gathers w_inc[i] = w[src_edge[i]]; thread 0 of block 0 adds the float partials in block order.
+// losses = (coef_e loss_e + coef_l loss_l, loss_e, loss_l); a mean over nothing is 0 / 0 = NaN, as F.mse_loss gives.
+__global__ __launch_bounds__(256) void edgeprob_batch_finish_kernel(
+    const float* __restrict__ part_e, const float* __restrict__ part_l, const int32_t* __restrict__ part_n, int32_t n_part,
+    int64_t k, int64_t n_cand, float coef_e, float coef_l, const float* __restrict__ raw, float* __restrict__ w,
+    float* __restrict__ losses, const int32_t* __restrict__ src_edge, const int64_t* __restrict__ inc_ptr, int64_t n_nodes,
+    float* __restrict__ w_inc) {
+#pragma clang fp contract(off)
+  __shared__ int32_t red_n[4];
+  int32_t c = 0;
+  for (int32_t i = threadIdx.x; i < n_part; i += 256) c += part_n[i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+  if ((threadIdx.x & 63) == 0) red_n[threadIdx.x >> 6] = c;
+  __syncthreads();
+  const int32_t n_l = (red_n[0] + red_n[1]) + (red_n[2] + red_n[3]);
+  const float scale_e = k > 0 ? coef_e * 2.0f / (float)k : 0.f;
+  const float scale_l = n_l > 0 ? coef_l * 2.0f / (float)n_l : 0.f;
+  const int64_t n_w = 2 * k + n_cand;
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+  // decoded entry e: e < k +diff_e, e < 2k -diff_{e-k}, else candidate e - 2k = item e - k
+  for (int64_t e = tid; e < n_w; e += stride)
+    w[e] = e < k ? scale_e * raw[e] : e < 2 * k ? -(scale_e * raw[e - k]) : scale_l * raw[e - k];
+  if (src_edge) {
+    int64_t total = inc_ptr[n_nodes];
+    if (total > 2 * n_w) total = 2 * n_w;           // (two incidences per decoded edge: the size of w_inc)
+    for (int64_t i = tid; i < total; i += stride) {
+      const int64_t e = src_edge[i];
+      float v = 0.f;
+      if (e >= 0 && e < n_w) v = e < k ? scale_e * raw[e] : e < 2 * k ? -(scale_e * raw[e - k]) : scale_l * raw[e - k];
+      w_inc[i] = v;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    float se = 0.f, sl = 0.f;
+    for (int32_t i = 0; i < n_part; ++i) { se += part_e[i]; sl += part_l[i]; }
+    const float loss_e = se / (float)k, loss_l = sl / (float)n_l;
+    losses[0] = coef_e * loss_e + coef_l * loss_l;
+    losses[1] = loss_e;
+    losses[2] = loss_l;
+  }
+}
+
+static inline int batch_loss_blocks(int64_t items, int lpr) {
+  const int64_t nb = dec_blocks(items > 0 ? items : 1, lpr);
+  return (int)(nb < kBatchLossMaxBlocks ? nb : kBatchLossMaxBlocks);
+}
+
 }  // namespace gd
 
 extern "C" int64_t gd_edgeprob_dec_workspace(int64_t m, int32_t d) {
@@ -271,6 +406,69 @@ extern "C" int gd_edge_incidence(const int64_t* e0, const int64_t* e1, int64_t n
   if ((rc = launched("inc_fill"))) return rc;
   hipLaunchKernelGGL(inc_rank_kernel, grid, dim3(256), 0, s, e0, e1, n_edges, n_nodes, inc_ptr, slots, other, src_edge);
   return launched("inc_rank");
+}
+
+extern "C" int64_t gd_edgeprob_batch_loss_workspace(int64_t k, int64_t n_cand, int32_t d) {
+  using namespace gd;
+  if (k < 0 || n_cand < 0 || k + n_cand >= (1ll << 28) || d <= 0 || d % 4) return -1;
+  return 3 * (int64_t)batch_loss_blocks(k + n_cand, lanes_per_row(d / 4)) + k + n_cand + 4;
+}
+
+extern "C" int gd_edgeprob_batch_loss_f32(const float* z, int64_t ld_z, int64_t n_nodes, const float* z_ori, int64_t ld_ori,
+                                          int64_t n_ori, int32_t d, const int64_t* pos, int64_t ld_pos, const int64_t* neg,
+                                          int64_t ld_neg, int64_t k, const int64_t* cand_src, const int64_t* cand_dst,
+                                          int64_t n_cand, float coef_e, float coef_l, int64_t* dec, int64_t ld_dec, float* w,
+                                          float* losses, int64_t* inc_ptr, int32_t* other, int32_t* src_edge, float* w_inc,
+                                          void* inc_workspace, int64_t inc_workspace_bytes, float* workspace, void* stream) {
+  using namespace gd;
+  GD_REQUIRE(z && z_ori && dec && w && losses && workspace, GD_E_NULL, "gd_edgeprob_batch_loss_f32: null pointer");
+  GD_REQUIRE(k >= 0 && n_cand >= 0 && k + n_cand < (1ll << 28), GD_E_DIM, "gd_edgeprob_batch_loss_f32: k=%lld n_cand=%lld out of range",
+             (long long)k, (long long)n_cand);
+  GD_REQUIRE((k == 0 || (pos && neg)) && (n_cand == 0 || (cand_src && cand_dst)), GD_E_NULL,
+             "gd_edgeprob_batch_loss_f32: null edge list");
+  const bool inc = inc_ptr != nullptr;
+  GD_REQUIRE(inc == (other != nullptr) && inc == (src_edge != nullptr) && inc == (w_inc != nullptr) && inc == (inc_workspace != nullptr),
+             GD_E_NULL, "gd_edgeprob_batch_loss_f32: inc_ptr, other, src_edge, w_inc and inc_workspace go together");
+  const int64_t n_w = 2 * k + n_cand;
+  GD_REQUIRE(n_nodes >= 1 && n_nodes < (1ll << 31) && n_ori >= 1 && d > 0 && d % 4 == 0 && d <= 4096 && ld_z >= d && ld_z % 4 == 0 &&
+                 ld_ori >= d && ld_ori % 4 == 0 && ld_pos >= k && ld_neg >= k && ld_dec >= n_w,
+             GD_E_DIM, "gd_edgeprob_batch_loss_f32: d=%d must be a multiple of 4 with 16-byte row pitches (ld_z=%lld, ld_ori=%lld)", d,
+             (long long)ld_z, (long long)ld_ori);
+  GD_REQUIRE(aligned16(z) && aligned16(z_ori), GD_E_ALIGN, "gd_edgeprob_batch_loss_f32: unaligned z / z_ori");
+  GD_REQUIRE(!inc || inc_workspace_bytes >= gd_edge_incidence_workspace(n_nodes, n_w), GD_E_WORKSPACE,
+             "gd_edgeprob_batch_loss_f32: incidence workspace of %lld bytes, %lld needed", (long long)inc_workspace_bytes,
+             (long long)gd_edge_incidence_workspace(n_nodes, n_w));
+  hipStream_t s = (hipStream_t)stream;
+  const int d4 = d / 4;
+  const int lpr = lanes_per_row(d4);
+  const int nb = batch_loss_blocks(k + n_cand, lpr);
+  float* part_e = workspace;
+  float* part_l = part_e + nb;
+  int32_t* part_n = reinterpret_cast<int32_t*>(part_l + nb);
+  float* raw = part_l + 2 * nb;
+#define GD_BL_CASE(LPR)                                                                                                          \
+  hipLaunchKernelGGL((edgeprob_batch_dots_kernel<LPR>), dim3(nb), dim3(256), 0, s, z, ld_z, n_nodes, z_ori, ld_ori, n_ori, d4, pos, \
+                     ld_pos, neg, ld_neg, k, cand_src, cand_dst, n_cand, dec, ld_dec, raw, part_e, part_l, part_n)
+  switch (lpr) {
+    case 1: GD_BL_CASE(1); break;
+    case 2: GD_BL_CASE(2); break;
+    case 4: GD_BL_CASE(4); break;
+    case 8: GD_BL_CASE(8); break;
+    case 16: GD_BL_CASE(16); break;
+    case 32: GD_BL_CASE(32); break;
+    default: GD_BL_CASE(64); break;
+  }
+#undef GD_BL_CASE
+  int rc = launched("edgeprob_batch_dots");
+  if (rc) return rc;
+  if (inc) {      // the list over all decoded edges: a candidate that does not count is (-1, -1) and gets no entries
+    rc = gd_edge_incidence(dec, dec + ld_dec, n_w, n_nodes, inc_ptr, other, src_edge, inc_workspace, inc_workspace_bytes, stream);
+    if (rc) return rc;
+  }
+  const int64_t fb = ((inc ? 2 : 1) * n_w + 255) / 256;
+  hipLaunchKernelGGL(edgeprob_batch_finish_kernel, dim3((unsigned)(fb > 1024 ? 1024 : fb < 1 ? 1 : fb)), dim3(256), 0, s, part_e,
+                     part_l, part_n, nb, k, n_cand, coef_e, coef_l, raw, w, losses, src_edge, inc_ptr, n_nodes, w_inc);
+  return launched("edgeprob_batch_finish");
 }
 
 extern "C" int gd_rows_add_f32(float* dz, int64_t ld_dz, int64_t n_rows, const int32_t* nodes, int32_t n_s, const float* src,

@@ -73,6 +73,15 @@ class GNNDeleteTrainer(Trainer):
             z_ori = self.get_embedding(model, dd)
         data.edge_index = data.train_pos_edge_index
         data.node_id = torch.arange(data.x.shape[0])
+        if getattr(args, 'fused_minibatch', False):
+            # --fused_minibatch: the same loop with each batch on the fused HIP batch step (gnndelete_amd/minibatch.py)
+            from ...minibatch import fused_minibatch_edgeprob_unsupported, train_minibatch_edgeprob_fused
+            reason = fused_minibatch_edgeprob_unsupported(model, args, optimizer)
+            if reason is None:
+                self.trainer_log['minibatch_step'] = 'fused'
+                return train_minibatch_edgeprob_fused(self, model, data, z_ori, optimizer, args)
+            print(f'--fused_minibatch: {reason}; running the autograd mini-batch loop', flush=True)
+            self.trainer_log['minibatch_step'] = 'autograd'
         loader = S.make_sampler(data, args.batch_size, args.num_steps)
         best_metric = 0
         self.trainer_log['steps'] = []

@@ -18,7 +18,12 @@ and Adam on the HIP kernels, fed by a device-side subgraph cut:
 
 Update order is the autograd loop's: loss1's gradient -> Adam on W_D1; loss2's gradient (W_D2's, and W_D1's, which is
 kept and added to the next batch's W_D1 gradient) -> Adam on W_D2.  The per-step losses stay on the device and become
-trainer_log['steps'] once per epoch."""
+trainer_log['steps'] once per epoch.
+
+MinibatchEdgeprobStep is the batch step of the edge-probability trainer (--unlearning_model gnndelete;
+framework/trainer/gnndelete.py:312-450) on the same cut, sdf CSR and layer helpers (_BatchStep): its loss stage is
+gd_edgeprob_batch_loss_f32 over [Df edges | negatives | the batch's S_Df edges with src < dst], its backward
+EdgeprobEngine's on the batch CSR, one Adam step on both Del weights."""
 import os
 
 import numpy as np
@@ -74,7 +79,8 @@ class BatchCut:
         node_flags = torch.zeros(self.n, dtype=torch.uint8)
         for bit, key in enumerate(['sdf_node_1hop_mask', 'sdf_node_2hop_mask', 'sdf_node_1hop_mask_non_df_mask',
                                    'sdf_node_2hop_mask_non_df_mask']):
-            node_flags |= getattr(data, key).to('cpu', torch.uint8) << bit
+            if hasattr(data, key):          # (the edge-probability loop has no NI rows: lists 2 and 3 stay empty)
+                node_flags |= getattr(data, key).to('cpu', torch.uint8) << bit
         self.node_flags = node_flags.to(dev)
         self.relabel = torch.zeros(self.n, dtype=torch.int64, device=dev)
         self.generation = 0
@@ -163,14 +169,14 @@ class BatchCut:
                              stream_ptr(self.dev)), 'gd_batch_csr')
         return g
 
-class MinibatchNodeembStep:
-    """Owns the per-run state of the fused batch step: a BatchCut, the frozen layer-1 transform of every node, the
-    Adam moments and the carried W_D1 gradient."""
+class _BatchStep:
+    """What the batch steps of both trainers share: a BatchCut, the frozen layer-1 transform of every node, the Adam
+    moments of the two Del weights, and the layer helpers over a batch CSR."""
 
-    def __init__(self, model, data, loader, alpha, lr, betas, eps, max_nodes=None):
+    def __init__(self, model, data, loader, lr, betas, eps, max_nodes=None):
         from .nn import GATConv
         dev = next(model.parameters()).device
-        self.dev, self.model, self.alpha = dev, model, float(alpha)
+        self.dev, self.model = dev, model
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.gat = isinstance(model.conv1, GATConv)
         self.cut = BatchCut(data, loader, dev, max_nodes)
@@ -198,7 +204,6 @@ class MinibatchNodeembStep:
                               'step': torch.zeros(1, dtype=torch.int32, device=dev), 'steps': 0})
         self.g1 = torch.zeros_like(self.wd1.data)
         self.g2 = torch.zeros_like(self.wd2.data)
-        self.g1_live = False            # W_D1 holds loss2's gradient of the previous batch (carried into the next step)
         self._bufs = {}
         self.events = None              # list -> (stage, cuda event) pairs are appended (stage split of the experiment)
 
@@ -256,6 +261,22 @@ class MinibatchNodeembStep:
         y, alpha = self._agg(g, h, scores, self.b2, self.slope2 if self.gat else 0.0)
         return y, h, scores, alpha
 
+    def _adam(self, k, p, grad):
+        st = self.adam[k]
+        check(_lib.lib().gd_adam_f32(ptr(p.data), ptr(grad), ptr(st['m']), ptr(st['v']), ptr(st['step']), p.numel(), self.lr,
+                                     self.betas[0], self.betas[1], self.eps, stream_ptr(self.dev)), 'gd_adam_f32')
+        st['steps'] += 1
+
+
+class MinibatchNodeembStep(_BatchStep):
+    """Owns the per-run state of the fused batch step: a BatchCut, the frozen layer-1 transform of every node, the
+    Adam moments and the carried W_D1 gradient."""
+
+    def __init__(self, model, data, loader, alpha, lr, betas, eps, max_nodes=None):
+        super().__init__(model, data, loader, lr, betas, eps, max_nodes)
+        self.alpha = float(alpha)
+        self.g1_live = False            # W_D1 holds loss2's gradient of the previous batch (carried into the next step)
+
     def _loss(self, z, z_ori, neg, n_pos, ni, n_ni, d, sums):
         """DEC + NI of one layer: sums[0] += sum of squared DEC differences, sums[1] += NI's; -> dz of alpha * DEC_mean +
         (1 - alpha) * NI_mean (a mean over zero rows has no gradient)."""
@@ -279,12 +300,6 @@ class MinibatchNodeembStep:
                                    ptr(term_o), ptr(term_w), ptr(term_kind), ptr(dz), dz.stride(0), 0, ptr(sums), ptr(part),
                                    stream_ptr(self.dev)), 'gd_rowpair_mse_f32')
         return dz
-
-    def _adam(self, k, p, grad):
-        st = self.adam[k]
-        check(_lib.lib().gd_adam_f32(ptr(p.data), ptr(grad), ptr(st['m']), ptr(st['v']), ptr(st['step']), p.numel(), self.lr,
-                                     self.betas[0], self.betas[1], self.eps, stream_ptr(self.dev)), 'gd_adam_f32')
-        st['steps'] += 1
 
     # ---------------------------------------------------------------------------------------------- one batch
     def step(self, nodes, sums):
@@ -442,3 +457,166 @@ def train_minibatch_fused(trainer, model, data, optimizer, args, step_hook=None)
     step.export_adam_state(optimizer)
     torch.save({'model_state': {k: v.to('cpu') for k, v in model.state_dict().items()}},
                os.path.join(args.checkpoint_dir, 'model_final.pt'))
+
+
+# ------------------------------------------------------------------------------------------------ edge-probability batches
+def fused_minibatch_edgeprob_unsupported(model, args, optimizer):
+    """None when the fused edge-probability batch step applies, else the reason it does not (one line): the rules of
+    edgeprob.fused_edgeprob_unsupported."""
+    from .edgeprob import fused_edgeprob_unsupported
+    reason = fused_edgeprob_unsupported(model, args, optimizer)
+    if reason is not None:
+        reason = reason.replace('fused edge-probability step', 'fused edge-probability batch step')
+    return reason
+
+
+class MinibatchEdgeprobStep(_BatchStep):
+    """The batch step of GNNDeleteTrainer.train_minibatch (the edge-probability loop): forward on the batch's S_Df edges,
+    gd_edgeprob_batch_loss_f32 over [Df edges | negatives | S_Df edges with src < dst] against z_ori - the embedding of
+    the WHOLE graph, read at the batch-local ids (upstream's quirk) -, EdgeprobEngine's backward on the batch CSR and one
+    Adam step on both Del weights."""
+
+    def __init__(self, model, data, loader, z_ori, lr, betas, eps, max_nodes=None):
+        super().__init__(model, data, loader, lr, betas, eps, max_nodes)
+        self.z_ori = ops._f32_rows(z_ori.detach().to(self.dev)).contiguous()
+        if self.H % 4 or self.O % 4 or self.z_ori.shape[1] != self.O:
+            raise ValueError(f'MinibatchEdgeprobStep: widths {self.H} / {self.O} must be multiples of 4')
+        self.z = None                   # the last batch's embedding (node_embeddings.pt)
+
+    def step(self, nodes, losses):
+        """One batch on `nodes`; losses [3] receives (0.5 loss_e + 0.5 loss_l, loss_e, loss_l) on the device."""
+        from .framework.trainer import sampler as S
+        L, dev = _lib.lib(), self.dev
+        self._mark('start')
+        c = self.cut
+        cnt = c.cut(nodes)
+        n_b, k, n_s1, n_s2, n_cand = cnt[0], cnt[3], cnt[4], cnt[5], cnt[9]
+        self._mark('cut')
+        g = c.batch_csr(True, self.gat)
+        self._mark('csr')
+        O = self.O
+        idx1, idx2 = c.rows(0, n_s1), c.rows(1, n_s2)
+        slope1, slope2 = (self.slope1, self.slope2) if self.gat else (0.0, 0.0)
+        # forward: frozen layer 1 gathered from the per-run table, Del 1 on S1, conv2 with the ReLU, Del 2 on S2
+        h1 = self.h1_all.index_select(0, c.nodes)
+        sc1 = None
+        if self.gat:
+            a1 = self.a1_all.index_select(0, c.nodes)
+            sc1 = (a1[:, 0].contiguous(), a1[:, 1].contiguous())
+        p1, _ = self._agg(g, h1, sc1, self.b1, slope1)
+        wd1, wd2 = self.wd1.data, self.wd2.data
+        z1 = p1.clone()
+        if n_s1:
+            ops.rows_gemm(p1, idx1, wd1, out=z1)
+        p2, h2, sc2, alpha2 = self._layer2(g, z1)
+        z2 = p2.clone()
+        if n_s2:
+            ops.rows_gemm(p2, idx2, wd2, out=z2)
+        self.z = z2
+        self._mark('forward')
+        edge_index, _ = c.batch_edges()
+        neg = S.negative_sampling(edge_index, n_b, k).to(dev, torch.int64).contiguous()
+        self._mark('negatives')
+        # loss stage: both terms, the incidence list of what counts, dL/dz2
+        n_w = 2 * k + n_cand
+        dec = torch.empty(2, max(n_w, 1), dtype=torch.int64, device=dev)
+        w = torch.empty(max(n_w, 1), dtype=torch.float32, device=dev)
+        w_inc = torch.empty(max(2 * n_w, 1), dtype=torch.float32, device=dev)
+        other = torch.empty(max(2 * n_w, 1), dtype=torch.int32, device=dev)
+        src_edge = torch.empty(max(2 * n_w, 1), dtype=torch.int32, device=dev)
+        inc_ptr = torch.empty(n_b + 1, dtype=torch.int64, device=dev)
+        inc_ws = self._ws('incidence', L.gd_edge_incidence_workspace(n_b, n_w))
+        ws = self._ws('loss', 4 * L.gd_edgeprob_batch_loss_workspace(k, n_cand, O))
+        check(L.gd_edgeprob_batch_loss_f32(ptr(z2), z2.stride(0), n_b, ptr(self.z_ori), self.z_ori.stride(0), self.z_ori.shape[0], O,
+                                           ptr(c.df_index), c.e_cap, ptr(neg), neg.stride(0) if k else 0, k, ptr(c.sdf_src),
+                                           ptr(c.sdf_dst), n_cand, 0.5, 0.5, ptr(dec), dec.stride(0), ptr(w), ptr(losses),
+                                           ptr(inc_ptr), ptr(other), ptr(src_edge), ptr(w_inc), ptr(inc_ws), inc_ws.numel(),
+                                           ptr(ws), stream_ptr(dev)), 'gd_edgeprob_batch_loss_f32')
+        gz = torch.empty(n_b, O, dtype=torch.float32, device=dev)
+        check(L.gd_edge_dot_bwd_f32(ptr(z2), z2.stride(0), O, ptr(other), ptr(w_inc), None, 0, None, ptr(inc_ptr), n_b, ptr(gz),
+                                    gz.stride(0), stream_ptr(dev)), 'gd_edge_dot_bwd_f32')
+        self._mark('loss')
+        # backward: Del 2, conv2 to its input, the ReLU gate folded into Del 1's weight gradient.  The Del layer's autograd node
+        # always returns a weight gradient (zeros without rows), so Adam steps both weights on every batch.
+        if n_s2:
+            ops.rows_gemm_wgrad(p2, idx2, gz, idx2, n_s2, out=self.g2)
+            ops.rows_gemm(gz, idx2, wd2, trans_w=True, out=gz)
+        else:
+            self.g2.zero_()
+        if n_s1:
+            dh2 = self._agg_bwd(g, h2, sc2, alpha2, gz, slope2, self.att2 if self.gat else None)
+            dx1 = ops.rows_gemm(dh2, None, self.w2)                  # [n_b, H], before the ReLU gate
+            ops.rows_gemm_wgrad(p1, idx1, dx1, idx1, n_s1, relu_mask=z1, out=self.g1)
+        else:
+            self.g1.zero_()
+        self._adam(0, self.wd1, self.g1)
+        self._adam(1, self.wd2, self.g2)
+        self._mark('backward')
+
+    # ---------------------------------------------------------------------------------------------- optimizer state
+    def import_adam_state(self, optimizer):
+        for st, p in zip(self.adam, (self.wd1, self.wd2)):
+            have = optimizer.state.get(p)
+            if have and 'exp_avg' in have:
+                st['m'].copy_(have['exp_avg'])
+                st['v'].copy_(have['exp_avg_sq'])
+                st['steps'] = int(have['step'])
+                st['step'].fill_(st['steps'])
+
+    def export_adam_state(self, optimizer):
+        """Adam moments and step count into the caller's optimizer; no gradient is kept (the loop's zero_grad)."""
+        for st, p in zip(self.adam, (self.wd1, self.wd2)):
+            if st['steps']:
+                optimizer.state[p] = {'step': torch.tensor(float(st['steps'])), 'exp_avg': st['m'].clone(),
+                                      'exp_avg_sq': st['v'].clone()}
+            p.grad = None
+
+
+def train_minibatch_edgeprob_fused(trainer, model, data, z_ori, optimizer, args, step_hook=None):
+    """The epoch loop of GNNDeleteTrainer.train_minibatch with the batch step on the HIP kernels: same sampler and
+    negatives (same random stream), same epoch records (upstream's double division and swapped names), model selection,
+    checkpoints and optimizer state.  data: on the host, edge_index / node_id set as the loop sets them."""
+    import time
+    from .framework.trainer import sampler as S
+    from .framework.trainer.base import device
+    from .framework.trainer.gnndelete_nodeemb import _adam_hyper
+    loader = S.make_sampler(data, args.batch_size, args.num_steps)
+    lr, betas, eps = _adam_hyper(optimizer)
+    step = MinibatchEdgeprobStep(model, data, loader, z_ori, lr, betas, eps,
+                                 max_nodes=(loader.walk_length + 1) * max(int(loader.batch_size), 1))
+    step.import_adam_state(optimizer)
+    trainer._fused_minibatch_step = step
+    best_metric = 0
+    trainer.trainer_log['steps'] = []
+    for epoch in range(args.epochs):
+        model.train()
+        start = time.time()
+        hist = torch.zeros(max(len(loader), 1), 3, dtype=torch.float32, device=device)
+        done = 0
+        for i, nodes in enumerate(loader.node_sets()):
+            if i >= hist.shape[0]:
+                hist = torch.cat([hist, torch.zeros_like(hist)])
+            step.step(nodes, hist[i])
+            done += 1
+            if step_hook is not None:
+                step_hook(step)
+        step_logs = [{'loss': r[0], 'loss_e': r[1], 'loss_l': r[2]} for r in hist[:done].tolist()]   # the epoch's host read
+        trainer.trainer_log['steps'].extend(step_logs)
+        if (epoch + 1) % args.valid_freq == 0:
+            step.export_adam_state(optimizer)               # (a checkpoint below carries the optimizer's state)
+            valid_loss, dt_auc, dt_aup, df_auc, df_aup, df_logit, _, valid_log = trainer.eval(model, data, 'val')
+            div = max(len(step_logs) - 1, 1)                # upstream divides by the last enumerate index, twice
+            tot = {k_: sum(s_[k_] for s_ in step_logs) / div for k_ in ('loss', 'loss_e', 'loss_l')}
+            trainer._record({'epoch': epoch, 'train_loss': tot['loss'] / div, 'train_loss_l': tot['loss_e'] / div,
+                             'train_loss_e': tot['loss_l'] / div, 'train_time': (time.time() - start) / div / div}, valid_log)
+            if dt_auc + df_auc > best_metric:
+                best_metric = dt_auc + df_auc
+                print(f'Save best checkpoint at epoch {epoch:04d}. Valid loss = {valid_loss:.4f}')
+                torch.save({'model_state': model.state_dict(), 'optimizer_state': optimizer.state_dict()},
+                           os.path.join(args.checkpoint_dir, 'model_best.pt'))
+                if step.z is not None:
+                    torch.save(step.z.detach(), os.path.join(args.checkpoint_dir, 'node_embeddings.pt'))
+            data = data.to('cpu')
+    step.export_adam_state(optimizer)
+    torch.save({'model_state': {k_: v.to('cpu') for k_, v in model.state_dict().items()},
+                'optimizer_state': optimizer.state_dict()}, os.path.join(args.checkpoint_dir, 'model_final.pt'))

@@ -52,7 +52,9 @@ extern "C" {
                                 gd_spmm_csr_onepass_wide_f32: 64-float rows summed 16 rows per item on the matrix pipe (entry added: the version stays);
                                 gd_negative_edges: negative edges drawn on the device (entry added: the version stays);
                                 gd_edge_incidence_fixed, gd_edge_incidence_update (+ their size queries): the incidence list when only
-                                the tail of the decoded edges changes (entries added: the version stays) */
+                                the tail of the decoded edges changes (entries added: the version stays);
+                                gd_edgeprob_batch_loss_f32 (+ its _workspace query): the loss stage of the edge-probability GraphSAINT
+                                batch step (entries added: the version stays) */
 
 enum {
   GD_OK = 0,
@@ -822,6 +824,36 @@ int gd_rows_add_f32(float* dz, int64_t ld_dz, int64_t n_rows, const int32_t* nod
  * hist: [capacity, 3] floats.  One thread; graph-capturable. */
 int gd_edgeprob_record_f32(const float* loss_r, const float* loss_l, float coef_r, float coef_l, float* hist,
                            int32_t capacity, int32_t* pos, void* stream);
+
+/* Loss stage of one GraphSAINT batch of the edge-probability mini-batch loop (GNNDeleteTrainer.train_minibatch,
+ * framework/trainer/gnndelete.py:364-400), value and logit gradients of both terms:
+ *     a_j = <z[pos[0][j]], z[pos[1][j]]>,  b_j = <z[neg[0][j]], z[neg[1][j]]>                               (j < k)
+ *     loss_e = (1/k)   sum_j (a_j - b_j)^2
+ *     loss_l = (1/n_l) sum_{c < n_cand: src_c < dst_c} (<z[src_c], z[dst_c]> - <z_ori[src_c], z_ori[dst_c]>)^2
+ *     losses = (coef_e loss_e + coef_l loss_l, loss_e, loss_l)
+ * The decoded list is [pos (k) | neg (k) | candidates (n_cand)]: dec, int64 [2, ld_dec] (ld_dec >= 2k + n_cand), receives
+ * it with (-1, -1) in place of every candidate that does not count (src >= dst), and w [2k + n_cand] receives
+ * d(coef_e loss_e + coef_l loss_l)/d(logit) in that order: w[j] = coef_e 2 (a_j - b_j) / k, w[k + j] = -w[j],
+ * w[2k + c] = coef_l 2 diff_c / n_l, exactly 0 for a candidate that does not count.  z_ori is its own table (pitch ld_ori,
+ * n_ori rows) read at the SAME ids as z.  n_l, the number of candidates with src < dst, is counted on the device in the
+ * same pass (integers).  k == 0 makes loss_e (and losses[0]) NaN with no gradient from it, n_l == 0 does the same for
+ * loss_l - F.mse_loss of nothing; neither is an error, and the other term's gradient is still written.  An endpoint
+ * outside its table ([0, n_nodes) for z, [0, n_ori) for z_ori) makes that dot product 0; nothing outside the tables is
+ * read.  With inc_ptr [n_nodes + 1] / other / src_edge / w_inc [2 (2k + n_cand)] / inc_workspace
+ * (gd_edge_incidence_workspace(n_nodes, 2k + n_cand) bytes) - all five or none - the entry also runs gd_edge_incidence
+ * over dec (a (-1, -1) edge gets no entries) and its finishing launch writes w_inc[i] = w[src_edge[i]] for every incidence
+ * i < inc_ptr[n_nodes]: what gd_edge_dot_bwd_f32 reads.  One lane group per item, float4 per lane, both tables of a
+ * candidate read by the same group; at most 2,048 blocks walk the items grid-strided, one partial per block, added in
+ * block order by one thread (no float atomics): the same bits every call.  workspace:
+ * gd_edgeprob_batch_loss_workspace(k, n_cand, d) floats (-1: sizes out of range).  d % 4 == 0, 16-byte aligned rows, any
+ * row pitch that is a multiple of 4 (GD_E_DIM / GD_E_ALIGN otherwise).  Two launches around gd_edge_incidence's. */
+int64_t gd_edgeprob_batch_loss_workspace(int64_t k, int64_t n_cand, int32_t d);
+int gd_edgeprob_batch_loss_f32(const float* z, int64_t ld_z, int64_t n_nodes, const float* z_ori, int64_t ld_ori, int64_t n_ori,
+                               int32_t d, const int64_t* pos, int64_t ld_pos, const int64_t* neg, int64_t ld_neg, int64_t k,
+                               const int64_t* cand_src, const int64_t* cand_dst, int64_t n_cand, float coef_e, float coef_l,
+                               int64_t* dec, int64_t ld_dec, float* w, float* losses, int64_t* inc_ptr, int32_t* other,
+                               int32_t* src_edge, float* w_inc, void* inc_workspace, int64_t inc_workspace_bytes,
+                               float* workspace, void* stream);
 
 /* ---------------------------------------------------------------- fused backbone step (csrc/linkpred.hip) ---- */
 
