@@ -59,6 +59,7 @@ PROTOTYPES = {
     'gd_rank1_add2_f32': (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _p, _p, _p, _p]),
     'gd_segment_sum_f32': (ctypes.c_int, [_p, _p, _p, _i32, _p, _p]),
     'gd_rows_gemm_f32': (ctypes.c_int, [_p, _i64, _p, _i32, _p, _i32, _i32, _i32, _p, _i32, _p, _i64, _p, _p]),
+    'gd_rows_gather_gemm_f32': (ctypes.c_int, [_p, _i64, _i64, _p, _i32, _p, _i32, _i32, _p, _i32, _p, _i64, _p]),
     'gd_rows_gemm_wgrad_workspace': (_i64, [_i32, _i32, _i32]),
     'gd_rows_gemm_ws_covers': (ctypes.c_int, [_i32, _i32, _i32]),
     'gd_rows_gemm_accumulate_f32': (ctypes.c_int, [_p, _i64, _p, _i32, _p, _i32, _i32, _i32, _p, _i64, _p]),

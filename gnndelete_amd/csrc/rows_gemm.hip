@@ -75,12 +75,16 @@ struct RowDots { const float* u1; const float* u2; float* o1; float* o2; };
 // first (per-wave time stamps: four waves with identical static work finish at 109 / 136 / 156 / 166 us), so with a
 // static tile-to-wave map the kernel lasts as long as its slowest wave; with the counter the waves that run ahead take
 // more tiles and all end together (split_lab: 60.0 vs 61.8 us at the Del-1 size, 77.8 vs 80.4 us at N rows).
-template <int NT, int MODE, bool SEL = false, int NP = 0, int KC = 0, bool QUEUE = false>
+// GATHER (MODE 0 without SEL only): the row map of gd_rows_gather_gemm_f32 - sample s reads row gidx[s] of `in` (64-bit ids,
+// one outside [0, n_in) stands for a row of zeros and reads row 0 instead) and writes row s of a compact `out`
+template <int NT, int MODE, bool SEL = false, int NP = 0, int KC = 0, bool QUEUE = false, bool GATHER = false>
 __global__ __launch_bounds__(QUEUE ? 1024 : kGemmThreads, (NP && KC) ? 2 : 4) void rows_gemm_mfma_kernel(
     const float* in, int64_t ld_in, const int32_t* __restrict__ idx, int32_t n_sel,
     const float* __restrict__ w, int32_t d_in, int32_t trans_w, const float* __restrict__ bias, int32_t relu_in,
     float* out, int64_t ld_out, float* __restrict__ save_in, const uint32_t* __restrict__ gate_bits,
-    uint32_t* __restrict__ sign_out, const float* in_alt, const uint8_t* __restrict__ sel, RowDots dots) {
+    uint32_t* __restrict__ sign_out, const float* in_alt, const uint8_t* __restrict__ sel, RowDots dots,
+    const int64_t* __restrict__ gidx, int32_t n_in) {
+  static_assert(!GATHER || (MODE == 0 && !SEL && !QUEUE), "the gathering row map is built for the plain product");
   extern __shared__ __attribute__((aligned(16))) float wl[];
   constexpr int d_out = 32 * NT;
   constexpr int kGemmThreads = QUEUE ? 1024 : gd::kGemmThreads;       // (shadows the namespace constant in here)
@@ -152,15 +156,23 @@ __global__ __launch_bounds__(QUEUE ? 1024 : kGemmThreads, (NP && KC) ? 2 : 4) vo
   // exposed index + HBM round trip.  All loads are unconditional (clamped rows), no branches.
   auto row_of = [&](int tile_) -> int32_t {       // 32-bit row ids: registers are the scarce resource here
     const int s_ = min(tile_ * 32 + r_lo, n_sel - 1);
+    if (GATHER) {
+      const int64_t g_ = gidx[s_];
+      return (g_ >= 0 && g_ < n_in) ? (int32_t)g_ : -1;       // -1: a row of zeros (the epilogue drops what row 0 gave)
+    }
     return idx ? idx[s_] : s_;
   };
   // row r is read from in_alt instead of in where sel[r] != 0 (a matrix whose rows live in two buffers)
   auto base_of = [&](int32_t r) -> const float* { return (SEL && sel[r]) ? in_alt : in; };
+  // this lane's 64 bytes of k chunk 0 of row r
+  auto src_of = [&](int32_t r) -> const float4* {
+    return reinterpret_cast<const float4*>(base_of(r) + (int64_t)(GATHER ? max(r, 0) : r) * ld_in) + khalf * 4;
+  };
   // ---- epilogue: D[i][j], j = lane&31 = sample, i = (r&3) + 8*(r>>2) + 4*(lane>>5) = feature
   auto epilogue = [&](f32x16 (&acc)[NT], int32_t row_cur, int s_a, bool live, const uint32_t (&gate_w)[NT], float r1a, float r1b) {
       // (feature 32t + 8q + 4 khalf + c sits in acc[t][4q + c]; bit b of word t of a row's packed
       //  sign / gate mask is feature 32t + b, so this lane owns bits 8q + 4 khalf + c of each word)
-      float* dst = out + (int64_t)row_cur * ld_out + 4 * khalf;
+      float* dst = out + (int64_t)(GATHER ? s_a : row_cur) * ld_out + 4 * khalf;
       constexpr bool want_dots = MODE == 3;
       // (the u vectors are the same for every tile: without the clobber LICM keeps all of them in registers)
       if (want_dots) asm volatile("" ::: "memory");
@@ -172,6 +184,7 @@ __global__ __launch_bounds__(QUEUE ? 1024 : kGemmThreads, (NP && KC) ? 2 : 4) vo
         for (int q = 0; q < 4; ++q) {
           float4 v = make_float4(acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]);
           const int n0 = 32 * t + 8 * q;
+          if (GATHER && row_cur < 0) v = f4_zero();
           if (bias) v = f4_add(v, *reinterpret_cast<const float4*>(bias + n0 + 4 * khalf));
           if (want_dots) {
             asm volatile("" ::: "memory");      // one pair of u loads in flight, not all 8 NT of them
@@ -215,7 +228,7 @@ __global__ __launch_bounds__(QUEUE ? 1024 : kGemmThreads, (NP && KC) ? 2 : 4) vo
     if (tile >= n_tiles) return;
     auto fetch = [&](int t_, float4 (&a)[4 * KC], int32_t& row) {
       row = row_of(min(t_, n_tiles - 1));
-      const float4* s0 = reinterpret_cast<const float4*>(base_of(row) + (int64_t)row * ld_in) + khalf * 4;
+      const float4* s0 = src_of(row);
 #pragma unroll
       for (int kc = 0; kc < KC; ++kc)
 #pragma unroll
@@ -320,15 +333,15 @@ __global__ __launch_bounds__(QUEUE ? 1024 : kGemmThreads, (NP && KC) ? 2 : 4) vo
   int32_t row_nxt = row_of(min(tile_nxt, n_tiles - 1));
   float4 a_next[4];
   {
-    const float4* src0 = reinterpret_cast<const float4*>(base_of(row_cur) + (int64_t)row_cur * ld_in) + khalf * 4;
+    const float4* src0 = src_of(row_cur);
 #pragma unroll
     for (int i = 0; i < 4; ++i) a_next[i] = src0[i];
   }
   for (; tile < n_tiles;) {
     const int s_a = tile * 32 + r_lo;
     const bool live = s_a < n_sel;
-    const float4* src = reinterpret_cast<const float4*>(base_of(row_cur) + (int64_t)row_cur * ld_in) + khalf * 4;
-    const float4* src_n = reinterpret_cast<const float4*>(base_of(row_nxt) + (int64_t)row_nxt * ld_in) + khalf * 4;
+    const float4* src = src_of(row_cur);
+    const float4* src_n = src_of(row_nxt);
     float4* sav = save_in ? reinterpret_cast<float4*>(save_in + (int64_t)s_a * d_in) + khalf * 4 : nullptr;
 
     f32x16 acc[NT];
@@ -423,22 +436,25 @@ __global__ __launch_bounds__(QUEUE ? 1024 : kGemmThreads, (NP && KC) ? 2 : 4) vo
 }
 
 // Fallback for dimensions the MFMA path does not cover: one wave per selected row, the row is
-// held in registers (so in/out may alias), one output column at a time.
+// held in registers (so in/out may alias), one output column at a time.  GATHER: the row map of the MFMA kernel's.
+template <bool GATHER = false>
 __global__ __launch_bounds__(256) void rows_gemm_scalar_kernel(
     const float* in, int64_t ld_in, const int32_t* __restrict__ idx, int32_t n_sel,
     const float* __restrict__ w, int32_t d_in, int32_t d_out, int32_t trans_w, const float* __restrict__ bias,
     int32_t relu_in, float* out, int64_t ld_out, float* __restrict__ save_in, const uint32_t* __restrict__ gate_bits,
-    uint32_t* __restrict__ sign_out, const float* in_alt, const uint8_t* __restrict__ sel) {
+    uint32_t* __restrict__ sign_out, const float* in_alt, const uint8_t* __restrict__ sel,
+    const int64_t* __restrict__ gidx, int32_t n_in) {
   constexpr int kMaxPerLane = 16;  // d_in <= 1024
   const int lane = threadIdx.x & 63;
   const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (s >= n_sel) return;
-  const int64_t row = idx ? idx[s] : s;
+  const int64_t row = GATHER ? gidx[s] : (idx ? idx[s] : s);
+  const bool zero_row = GATHER && (row < 0 || row >= n_in);          // reads nothing, gives zeros (+ bias)
   float xr[kMaxPerLane];
 #pragma unroll
   for (int q = 0; q < kMaxPerLane; ++q) {
     const int k = lane + q * kWave;
-    float v = k < d_in ? ((sel && sel[row]) ? in_alt : in)[row * ld_in + k] : 0.f;
+    float v = (k < d_in && !zero_row) ? ((!GATHER && sel && sel[row]) ? in_alt : in)[row * ld_in + k] : 0.f;
     if (save_in && k < d_in) save_in[(int64_t)s * d_in + k] = v;
     xr[q] = relu_in ? fmaxf(v, 0.f) : v;
   }
@@ -452,11 +468,12 @@ __global__ __launch_bounds__(256) void rows_gemm_scalar_kernel(
       if (k < d_in) p = fmaf(xr[q], trans_w ? w[(int64_t)j * d_in + k] : w[(int64_t)k * d_out + j], p);
     }
     p = wave_sum(p);
+    if (zero_row) p = 0.f;
     p += bias ? bias[j] : 0.f;
     if (gate_bits && !((gate_bits[(int64_t)s * n_words + (j >> 5)] >> (j & 31)) & 1u)) p = 0.f;
     if (p > 0.f) word |= 1u << (j & 31);
     if (lane == 0) {
-      out[row * ld_out + j] = p;
+      out[(GATHER ? (int64_t)s : row) * ld_out + j] = p;
       if (sign_out && ((j & 31) == 31 || j == d_out - 1)) sign_out[(int64_t)s * n_words + (j >> 5)] = word;
     }
     if ((j & 31) == 31) word = 0;
@@ -876,7 +893,8 @@ static int rows_gemm_impl(const float* in, int64_t ld_in, const int32_t* idx, in
                           int32_t d_in, int32_t d_out, int32_t trans_w, const float* bias, int32_t relu_in,
                           const uint32_t* gate_bits, uint32_t* sign_out, float* out, int64_t ld_out,
                           float* save_in, void* stream, const float* in_alt = nullptr, const uint8_t* sel = nullptr,
-                          gd::RowDots dots = gd::RowDots{nullptr, nullptr, nullptr, nullptr}) {
+                          gd::RowDots dots = gd::RowDots{nullptr, nullptr, nullptr, nullptr}, const int64_t* gidx = nullptr,
+                          int32_t n_in = 0) {
   using namespace gd;
   GD_REQUIRE(!sel || (in_alt && aligned16(in_alt) && in_alt != out && !gate_bits && !sign_out), GD_E_NULL,
              "gd_rows_gemm_select_f32: bad in_alt");
@@ -886,7 +904,7 @@ static int rows_gemm_impl(const float* in, int64_t ld_in, const int32_t* idx, in
   GD_REQUIRE(in != out || d_in == d_out, GD_E_DIM, "gd_rows_gemm_f32: in-place needs d_in == d_out");
   GD_REQUIRE(!(gate_bits && sign_out), GD_E_DIM, "gd_rows_gemm_f32: gate and sign output are exclusive");
   if (n_sel == 0) return GD_OK;
-  {   // the Del operator's widths at step size: weight-stationary register form (rows_gemm_ws.hip)
+  if (!gidx) {   // the Del operator's widths at step size: weight-stationary register form (rows_gemm_ws.hip)
     const int rc = rows_gemm_ws_try(in, ld_in, idx, n_sel, w, d_in, d_out, trans_w, bias, relu_in, gate_bits, sign_out, out, ld_out,
                                     save_in, stream, in_alt, sel, dots.u1, dots.u2, dots.o1, dots.o2);
     if (rc != 1) return rc;
@@ -916,43 +934,44 @@ static int rows_gemm_impl(const float* in, int64_t ld_in, const int32_t* idx, in
     }
     // tile queue (one 16-wave block per CU) where a block gets enough tiles to hand out: the step's N- and S-row products
     static const bool queue_on = [] { const char* e = getenv("GD_ROWS_GEMM_QUEUE"); return !(e && atoi(e) == 0); }();
-    const bool use_queue = queue_on && !kc_split && !narrow_split && n_tiles >= 16 * 256;
+    const bool use_queue = queue_on && !kc_split && !narrow_split && n_tiles >= 16 * 256 && !gidx;
     if (use_queue && grid > ws_cu_count()) grid = ws_cu_count();            // one 16-wave block per compute unit
-#define GD_RG_KERNEL(NT, MODE, SELV, NPV, KCV)                                                                    \
+#define GD_RG_KERNEL(NT, MODE, SELV, NPV, KCV, GV)                                                                 \
   do {                                                                                                            \
-    if (use_queue && !NPV) {                                                                                      \
+    if (use_queue && !NPV && !GV) {                                                                                 \
       auto kq = rows_gemm_mfma_kernel<NT, MODE, SELV, 0, 0, true>;                                                \
       /* the tile counter is static LDS on top of the dynamic weight image (exactly 64 KB at 128 x 128) */        \
       static const hipError_t onceq = hipFuncSetAttribute((const void*)kq, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024 + 64); \
       GD_REQUIRE(onceq == hipSuccess, -(int)onceq, "gd_rows_gemm_f32: cannot raise the LDS limit of the tile-queue kernel"); \
       hipLaunchKernelGGL(kq, dim3(grid), dim3(1024), lds, s, in, ld_in, idx, n_sel, w, d_in, trans_w,             \
-                         bias, relu_in, out, ld_out, save_in, gate_bits, sign_out, in_alt, sel, dots);            \
+                         bias, relu_in, out, ld_out, save_in, gate_bits, sign_out, in_alt, sel, dots, gidx, n_in); \
       break;                                                                                                      \
     }                                                                                                             \
-    auto kern = rows_gemm_mfma_kernel<NT, MODE, SELV, NPV, KCV>;                                                  \
+    auto kern = rows_gemm_mfma_kernel<NT, MODE, SELV, NPV, KCV, false, GV>;                                            \
     if (NPV && lds > 64 * 1024) {                                                                                 \
       static const hipError_t once = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
       GD_REQUIRE(once == hipSuccess, -(int)once, "gd_rows_gemm_f32: cannot raise the LDS limit");                \
     }                                                                                                             \
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kGemmThreads), lds, s, in, ld_in, idx, n_sel, w, d_in, trans_w,     \
-                       bias, relu_in, out, ld_out, save_in, gate_bits, sign_out, in_alt, sel, dots);              \
+                       bias, relu_in, out, ld_out, save_in, gate_bits, sign_out, in_alt, sel, dots, gidx, n_in);  \
   } while (0)
-#define GD_RG_LAUNCH(NT, MODE, SELV)                                                                              \
+#define GD_RG_LAUNCH(NT, MODE, SELV, GV)                                                                          \
   do {                                                                                                            \
-    if (kc_split == 4) GD_RG_KERNEL(NT, MODE, SELV, 6, 4);                                                        \
-    else if (kc_split == 2) GD_RG_KERNEL(NT, MODE, SELV, 6, 2);                                                   \
-    else if (narrow_split && NT == 2) GD_RG_KERNEL(2, MODE, SELV, 6, 0);                                          \
-    else GD_RG_KERNEL(NT, MODE, SELV, 0, 0);                                                                      \
+    if (kc_split == 4) GD_RG_KERNEL(NT, MODE, SELV, 6, 4, GV);                                                     \
+    else if (kc_split == 2) GD_RG_KERNEL(NT, MODE, SELV, 6, 2, GV);                                                \
+    else if (narrow_split && NT == 2) GD_RG_KERNEL(2, MODE, SELV, 6, 0, GV);                                       \
+    else GD_RG_KERNEL(NT, MODE, SELV, 0, 0, GV);                                                                   \
   } while (0)
 #define GD_RG_CASE(NT)                                                                                            \
   do {                                                                                                            \
-    if (gate_bits && dots.u1) GD_RG_LAUNCH(NT, 4, false);                                                         \
-    else if (gate_bits) GD_RG_LAUNCH(NT, 2, false);                                                               \
-    else if (sign_out) GD_RG_LAUNCH(NT, 1, false);                                                                \
-    else if (dots.u1 && sel) GD_RG_LAUNCH(NT, 3, true);                                                           \
-    else if (dots.u1) GD_RG_LAUNCH(NT, 3, false);                                                                 \
-    else if (sel) GD_RG_LAUNCH(NT, 0, true);                                                                      \
-    else GD_RG_LAUNCH(NT, 0, false);                                                                              \
+    if (gidx) GD_RG_LAUNCH(NT, 0, false, true);                                                                   \
+    else if (gate_bits && dots.u1) GD_RG_LAUNCH(NT, 4, false, false);                                                   \
+    else if (gate_bits) GD_RG_LAUNCH(NT, 2, false, false);                                                        \
+    else if (sign_out) GD_RG_LAUNCH(NT, 1, false, false);                                                         \
+    else if (dots.u1 && sel) GD_RG_LAUNCH(NT, 3, true, false);                                                    \
+    else if (dots.u1) GD_RG_LAUNCH(NT, 3, false, false);                                                          \
+    else if (sel) GD_RG_LAUNCH(NT, 0, true, false);                                                               \
+    else GD_RG_LAUNCH(NT, 0, false, false);                                                                       \
   } while (0)
     switch (d_out / 32) {
       case 1: GD_RG_CASE(1); break;
@@ -968,8 +987,12 @@ static int rows_gemm_impl(const float* in, int64_t ld_in, const int32_t* idx, in
   GD_REQUIRE(!dots.u1, GD_E_DIM, "gd_rows_gemm_dots_f32: needs the MFMA path (d_in, d_out multiples of 32, d_out <= 128, "
              "weight <= 64 KB, 16-byte aligned rows)");
   GD_REQUIRE(d_in <= 1024, GD_E_DIM, "gd_rows_gemm_f32: fallback path needs d_in <= 1024 (got %d)", d_in);
-  hipLaunchKernelGGL(rows_gemm_scalar_kernel, dim3((n_sel + 3) / 4), dim3(256), 0, s, in, ld_in, idx, n_sel, w, d_in,
-                     d_out, trans_w, bias, relu_in, out, ld_out, save_in, gate_bits, sign_out, in_alt, sel);
+  if (gidx)
+    hipLaunchKernelGGL(rows_gemm_scalar_kernel<true>, dim3((n_sel + 3) / 4), dim3(256), 0, s, in, ld_in, idx, n_sel, w, d_in,
+                       d_out, trans_w, bias, relu_in, out, ld_out, save_in, gate_bits, sign_out, in_alt, sel, gidx, n_in);
+  else
+    hipLaunchKernelGGL(rows_gemm_scalar_kernel<false>, dim3((n_sel + 3) / 4), dim3(256), 0, s, in, ld_in, idx, n_sel, w, d_in,
+                       d_out, trans_w, bias, relu_in, out, ld_out, save_in, gate_bits, sign_out, in_alt, sel, gidx, n_in);
   return launched("rows_gemm_scalar");
 }
 
@@ -978,6 +1001,18 @@ extern "C" int gd_rows_gemm_f32(const float* in, int64_t ld_in, const int32_t* i
                                 float* out, int64_t ld_out, float* save_in, void* stream) {
   return rows_gemm_impl(in, ld_in, idx, n_sel, w, d_in, d_out, trans_w, bias, relu_in, nullptr, nullptr, out, ld_out,
                         save_in, stream);
+}
+
+extern "C" int gd_rows_gather_gemm_f32(const float* in, int64_t ld_in, int64_t n_in, const int64_t* idx, int32_t n_sel,
+                                       const float* w, int32_t d_in, int32_t d_out, const float* bias, int32_t relu_in,
+                                       float* out, int64_t ld_out, void* stream) {
+  GD_REQUIRE(in && w && (n_sel == 0 || (idx && out)), GD_E_NULL, "gd_rows_gather_gemm_f32: null pointer");
+  if (n_sel == 0) return GD_OK;                 // (an empty list and an empty result have no address)
+  GD_REQUIRE(in != out, GD_E_DIM, "gd_rows_gather_gemm_f32: in and out must not alias (rows are read while others are written)");
+  GD_REQUIRE(n_in >= 0 && n_in <= INT32_MAX && (n_in > 0 || n_sel <= 0), GD_E_DIM,
+             "gd_rows_gather_gemm_f32: n_in=%lld (1 .. 2^31 - 1 rows)", (long long)n_in);
+  return rows_gemm_impl(in, ld_in, nullptr, n_sel, w, d_in, d_out, 1, bias, relu_in, nullptr, nullptr, out, ld_out, nullptr,
+                        stream, nullptr, nullptr, gd::RowDots{nullptr, nullptr, nullptr, nullptr}, idx, (int32_t)n_in);
 }
 
 extern "C" int gd_rows_gemm_select_f32(const float* in, const float* in_alt, const uint8_t* sel, int64_t ld_in,

@@ -129,6 +129,15 @@ class Trainer:
         edge; best-validation-loss checkpoint."""
         from . import sampler as _sampler
         _require_gpu()
+        if getattr(args, 'fused_minibatch', False):
+            # --fused_minibatch: the same loop with each batch on the fused HIP batch step (gnndelete_amd/minibatch.py)
+            from ...minibatch import fused_minibatch_backbone_unsupported, train_minibatch_backbone_fused
+            reason = fused_minibatch_backbone_unsupported(model, args, optimizer)
+            if reason is None:
+                self.trainer_log['minibatch_step'] = 'fused'
+                return train_minibatch_backbone_fused(self, model, data, optimizer, args)
+            print(f'--fused_minibatch: {reason}; running the autograd mini-batch loop', flush=True)
+            self.trainer_log['minibatch_step'] = 'autograd'
         start = time.time()
         best_valid_loss, best_epoch = 1000000, 0
         model = model.to(device)

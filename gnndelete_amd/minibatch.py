@@ -23,7 +23,13 @@ trainer_log['steps'] once per epoch.
 MinibatchEdgeprobStep is the batch step of the edge-probability trainer (--unlearning_model gnndelete;
 framework/trainer/gnndelete.py:312-450) on the same cut, sdf CSR and layer helpers (_BatchStep): its loss stage is
 gd_edgeprob_batch_loss_f32 over [Df edges | negatives | the batch's S_Df edges with src < dst], its backward
-EdgeprobEngine's on the batch CSR, one Adam step on both Del weights."""
+EdgeprobEngine's on the batch CSR, one Adam step on both Del weights.
+
+MinibatchBackboneStep is the batch step of the ORIGINAL model's training (train_gnn.py --minibatch --fused_minibatch;
+framework/trainer/base.py:144-227): every parameter trains, so there is no frozen layer-1 table - each batch computes
+x[nodes] W1^T with the current W1 (gd_rows_gather_gemm_f32), runs both layers over the CSR of all batch edges, the BCE
+link-prediction loss over [batch edges | negatives] (gd_edge_bce_f32) and BackboneEngine's backward, then Adam on every
+parameter."""
 import os
 
 import numpy as np
@@ -73,9 +79,12 @@ class BatchCut:
         # the sampler's source-major CSR (sorted by (src, dst), stable ties) and one flag byte per edge in that order
         self.rowptr32 = loader.rowptr.to(device=dev, dtype=torch.int32).contiguous()
         self.col32 = loader.dst_sorted.to(device=dev, dtype=torch.int32).contiguous()
-        order = loader.order.to(data.sdf_mask.device)
-        flags = data.sdf_mask.to(torch.uint8) | (data.df_mask.to(torch.uint8) << 1)
-        self.edge_flags = flags[order].to(dev).contiguous()
+        if hasattr(data, 'sdf_mask') and hasattr(data, 'df_mask'):
+            order = loader.order.to(data.sdf_mask.device)
+            flags = data.sdf_mask.to(torch.uint8) | (data.df_mask.to(torch.uint8) << 1)
+            self.edge_flags = flags[order].to(dev).contiguous()
+        else:                               # (the backbone's batches: no request, no flagged edge)
+            self.edge_flags = torch.zeros(self.col32.numel(), dtype=torch.uint8, device=dev)
         node_flags = torch.zeros(self.n, dtype=torch.uint8)
         for bit, key in enumerate(['sdf_node_1hop_mask', 'sdf_node_2hop_mask', 'sdf_node_1hop_mask_non_df_mask',
                                    'sdf_node_2hop_mask_non_df_mask']):
@@ -169,9 +178,65 @@ class BatchCut:
                              stream_ptr(self.dev)), 'gd_batch_csr')
         return g
 
-class _BatchStep:
-    """What the batch steps of both trainers share: a BatchCut, the frozen layer-1 transform of every node, the Adam
-    moments of the two Del weights, and the layer helpers over a batch CSR."""
+class _BatchLayers:
+    """The layer helpers over a batch CSR that every batch step shares (self.dev, self.gat, self._bufs, self.events)."""
+
+    def _ws(self, key, nbytes):
+        if nbytes < 0:
+            raise ValueError(f'{key}: batch too large for int32 indices')
+        buf = self._bufs.get(key)
+        if buf is None or buf.numel() < nbytes:
+            buf = self._bufs[key] = torch.empty(max(256, _grow(nbytes)), dtype=torch.uint8, device=self.dev)
+        return buf
+
+    def _mark(self, stage):
+        if self.events is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self.events.append((stage, ev))
+
+    # ---------------------------------------------------------------------------------------------- layers
+    def _agg(self, g, h, scores, bias, slope):
+        """GCNConv / GATConv aggregation of transformed rows h over a batch CSR -> (y, saved attention or None)."""
+        y = torch.empty(g.n, h.shape[1], dtype=torch.float32, device=self.dev)
+        if not self.gat:
+            check(_lib.lib().gd_spmm_csr_f32(ptr(g.rowptr), ptr(g.col), ptr(g.val), ptr(h), h.stride(0), ptr(y), y.stride(0),
+                                             ptr(bias), 0.0, g.n, h.shape[1], stream_ptr(self.dev)), 'gd_spmm_csr_f32')
+            return y, None
+        a_src, a_dst = scores
+        alpha = torch.empty(g.nnz, dtype=torch.float32, device=self.dev)
+        check(_lib.lib().gd_gat_aggregate_f32(ptr(g.rowptr), ptr(g.col), ptr(a_src), ptr(a_dst), ptr(h), h.stride(0), ptr(y),
+                                              y.stride(0), ptr(bias), ptr(alpha), float(slope), g.n, h.shape[1],
+                                              stream_ptr(self.dev)), 'gd_gat_aggregate_f32')
+        return y, alpha
+
+    def _agg_bwd(self, g, h, scores, alpha, dy, slope, att, att_grads=None):
+        """Input gradient of _agg with respect to h (GAT: message path + the score terms' rank-1 rows).  att_grads (GAT): the
+        two buffers that receive the attention vectors' gradients, colsum(h, row_w = d a_src / d a_dst)."""
+        n, d = g.n, dy.shape[1]
+        if not self.gat:
+            dh = torch.empty(n, d, dtype=torch.float32, device=self.dev)
+            check(_lib.lib().gd_spmm_csr_f32(ptr(g.rowptr_t), ptr(g.col_t), ptr(g.val_t), ptr(dy), dy.stride(0), ptr(dh),
+                                             dh.stride(0), None, 0.0, n, d, stream_ptr(self.dev)), 'gd_spmm_csr_f32')
+            return dh
+        a_src, a_dst = scores
+        dh = torch.empty(n, d, dtype=torch.float32, device=self.dev)
+        da = torch.empty(2, n, dtype=torch.float32, device=self.dev)
+        de = torch.empty(g.nnz, dtype=torch.float32, device=self.dev)
+        check(_lib.lib().gd_gat_aggregate_bwd_f32(ptr(g.rowptr), ptr(g.col), ptr(alpha), ptr(g.rowptr_t), ptr(g.col_t),
+                                                  ptr(g.perm_t), ptr(a_src), ptr(a_dst), ptr(h), h.stride(0), ptr(dy),
+                                                  dy.stride(0), ptr(dh), dh.stride(0), ptr(da[0]), ptr(da[1]), ptr(de),
+                                                  float(slope), n, d, stream_ptr(self.dev)), 'gd_gat_aggregate_bwd_f32')
+        if att_grads is not None:
+            from .backbone import col_sum
+            for k in (0, 1):
+                col_sum(h, row_w=da[k], out=att_grads[k].view(-1))
+        return ops.rank1_add2_(dh, da[0], att[0], da[1], att[1])
+
+
+class _BatchStep(_BatchLayers):
+    """What the batch steps of both unlearning trainers share: a BatchCut, the frozen layer-1 transform of every node and
+    the Adam moments of the two Del weights."""
 
     def __init__(self, model, data, loader, lr, betas, eps, max_nodes=None):
         from .nn import GATConv
@@ -206,53 +271,6 @@ class _BatchStep:
         self.g2 = torch.zeros_like(self.wd2.data)
         self._bufs = {}
         self.events = None              # list -> (stage, cuda event) pairs are appended (stage split of the experiment)
-
-    def _ws(self, key, nbytes):
-        if nbytes < 0:
-            raise ValueError(f'{key}: batch too large for int32 indices')
-        buf = self._bufs.get(key)
-        if buf is None or buf.numel() < nbytes:
-            buf = self._bufs[key] = torch.empty(max(256, _grow(nbytes)), dtype=torch.uint8, device=self.dev)
-        return buf
-
-    def _mark(self, stage):
-        if self.events is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            self.events.append((stage, ev))
-
-    # ---------------------------------------------------------------------------------------------- layers
-    def _agg(self, g, h, scores, bias, slope):
-        """GCNConv / GATConv aggregation of transformed rows h over a batch CSR -> (y, saved attention or None)."""
-        y = torch.empty(g.n, h.shape[1], dtype=torch.float32, device=self.dev)
-        if not self.gat:
-            check(_lib.lib().gd_spmm_csr_f32(ptr(g.rowptr), ptr(g.col), ptr(g.val), ptr(h), h.stride(0), ptr(y), y.stride(0),
-                                             ptr(bias), 0.0, g.n, h.shape[1], stream_ptr(self.dev)), 'gd_spmm_csr_f32')
-            return y, None
-        a_src, a_dst = scores
-        alpha = torch.empty(g.nnz, dtype=torch.float32, device=self.dev)
-        check(_lib.lib().gd_gat_aggregate_f32(ptr(g.rowptr), ptr(g.col), ptr(a_src), ptr(a_dst), ptr(h), h.stride(0), ptr(y),
-                                              y.stride(0), ptr(bias), ptr(alpha), float(slope), g.n, h.shape[1],
-                                              stream_ptr(self.dev)), 'gd_gat_aggregate_f32')
-        return y, alpha
-
-    def _agg_bwd(self, g, h, scores, alpha, dy, slope, att):
-        """Input gradient of _agg with respect to h (GAT: message path + the score terms' rank-1 rows)."""
-        n, d = g.n, dy.shape[1]
-        if not self.gat:
-            dh = torch.empty(n, d, dtype=torch.float32, device=self.dev)
-            check(_lib.lib().gd_spmm_csr_f32(ptr(g.rowptr_t), ptr(g.col_t), ptr(g.val_t), ptr(dy), dy.stride(0), ptr(dh),
-                                             dh.stride(0), None, 0.0, n, d, stream_ptr(self.dev)), 'gd_spmm_csr_f32')
-            return dh
-        a_src, a_dst = scores
-        dh = torch.empty(n, d, dtype=torch.float32, device=self.dev)
-        da = torch.empty(2, n, dtype=torch.float32, device=self.dev)
-        de = torch.empty(g.nnz, dtype=torch.float32, device=self.dev)
-        check(_lib.lib().gd_gat_aggregate_bwd_f32(ptr(g.rowptr), ptr(g.col), ptr(alpha), ptr(g.rowptr_t), ptr(g.col_t),
-                                                  ptr(g.perm_t), ptr(a_src), ptr(a_dst), ptr(h), h.stride(0), ptr(dy),
-                                                  dy.stride(0), ptr(dh), dh.stride(0), ptr(da[0]), ptr(da[1]), ptr(de),
-                                                  float(slope), n, d, stream_ptr(self.dev)), 'gd_gat_aggregate_bwd_f32')
-        return ops.rank1_add2_(dh, da[0], att[0], da[1], att[1])
 
     def _layer2(self, g, z1):
         """conv2(relu(z1)) over g -> (y, h, scores, saved attention)."""
@@ -620,3 +638,227 @@ def train_minibatch_edgeprob_fused(trainer, model, data, z_ori, optimizer, args,
     step.export_adam_state(optimizer)
     torch.save({'model_state': {k_: v.to('cpu') for k_, v in model.state_dict().items()},
                 'optimizer_state': optimizer.state_dict()}, os.path.join(args.checkpoint_dir, 'model_final.pt'))
+
+
+# ------------------------------------------------------------------------------------------------ backbone batches
+def fused_minibatch_backbone_unsupported(model, args, optimizer):
+    """None when the fused backbone batch step applies (Trainer.train_minibatch with --fused_minibatch), else the reason it
+    does not (one line): the rules of backbone.fused_backbone_unsupported for a model that trains on batches."""
+    from .framework.trainer.sampler import data_parallel_world
+    from .nn import GATConv, GCNConv
+    conv1, conv2 = getattr(model, 'conv1', None), getattr(model, 'conv2', None)
+    if (not (isinstance(conv1, (GCNConv, GATConv)) and type(conv1) is type(conv2)) or hasattr(model, 'deletion1')
+            or hasattr(model, 'node_emb')):
+        return f'no fused backbone batch step for the {type(model).__name__} backbone (GCN and GAT only)'
+    if data_parallel_world()[1] > 1:
+        return 'torch.distributed with more than one rank'
+    if isinstance(optimizer, (list, tuple)) or type(optimizer) is not torch.optim.Adam or len(optimizer.param_groups) != 1:
+        return 'the optimizer is not one plain torch.optim.Adam'
+    g = optimizer.param_groups[0]
+    if g.get('weight_decay', 0):
+        return 'Adam with weight decay'
+    if g.get('amsgrad') or g.get('maximize'):
+        return 'Adam with amsgrad / maximize'
+    if {id(p) for p in g['params']} != {id(p) for p in model.parameters()} or not all(p.requires_grad for p in g['params']):
+        return 'the optimizer does not hold exactly the model\'s parameters'
+    hid, out = conv1.out_channels, conv2.out_channels
+    if hid % 4 or out % 4 or max(hid, out) > 1024:
+        return f'widths {hid} / {out} (multiples of 4 up to 1024)'
+    if conv1.in_channels > 1024:
+        return f'input width {conv1.in_channels} (the gathering first product takes up to 1024)'
+    return None
+
+
+class MinibatchBackboneStep(_BatchLayers):
+    """One batch of Trainer.train_minibatch (BCE link prediction on the batch's edges against one negative per edge) with an
+    explicit forward, BackboneEngine's hand-derived backward and the library's Adam on every parameter of the model, which
+    is stepped in place.  Shapes change per batch: eager launches, no captured graph.
+
+      cut, CSR over all batch edges;  t1 = x[nodes] W1^T (gd_rows_gather_gemm_f32: layer 1 trains, no per-run table);
+      p1 = A t1 + b1;  t2 = relu(p1) W2^T;  z = A t2 + b2 (GAT: row dots + gd_gat_aggregate_f32 per layer);
+      negatives from sampler.negative_sampling;  incidence list over [edges | negatives];  gd_edge_bce_f32 -> the caller's
+      loss slot;  g = dL/dz;  the backward of BackboneEngine._iteration_gcn / _iteration_gat on the batch CSR, dW1 = q1^T
+      x[nodes] through the weight-gradient entry's index list;  one gd_adam_f32 per parameter."""
+
+    def __init__(self, model, data, loader, lr, betas, eps, max_nodes=None):
+        from .nn import GATConv
+        dev = next(model.parameters()).device
+        self.dev, self.model = dev, model
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        c1, c2 = self.convs = (model.conv1, model.conv2)
+        self.gat = isinstance(c1, GATConv)
+        self.cut = BatchCut(data, loader, dev, max_nodes)
+        self.x = ops._f32_rows(data.x.to(dev, torch.float32))
+        self.w1, self.w2 = ((c.lin_src if self.gat else c.lin).weight for c in self.convs)         # [H, F], [O, H]
+        F_in, H, O = self.F, self.H, self.O = int(self.w1.shape[1]), int(self.w1.shape[0]), int(self.w2.shape[0])
+        if H % 4 or O % 4 or max(H, O, F_in) > 1024 or int(self.x.shape[1]) != F_in or int(self.w2.shape[1]) != H:
+            raise ValueError(f'MinibatchBackboneStep: widths {F_in} -> {H} -> {O} (hidden and output: multiples of 4; all up '
+                             'to 1024)')
+        self.params = list(model.parameters())
+        self.grads = {id(p): torch.zeros_like(p.data) for p in self.params}
+        self.adam = [{'m': torch.zeros_like(p.data), 'v': torch.zeros_like(p.data),
+                      'step': torch.zeros(1, dtype=torch.int32, device=dev), 'steps': 0} for p in self.params]
+        self._bufs = {}
+        self.events = None              # list -> (stage, cuda event) pairs are appended (stage split of the experiment)
+        self.z = None                   # the last batch's embedding (node_embeddings.pt)
+
+    def _grad(self, p):
+        return self.grads[id(p)]
+
+    def _att(self, c):
+        return c.att_src.data.view(-1), c.att_dst.data.view(-1)
+
+    def _layer(self, k, g, h):
+        """conv k's aggregation of the transformed rows h -> (y, scores, saved attention)."""
+        c = self.convs[k]
+        scores = ops.row_dots(h, *self._att(c)) if self.gat else None
+        y, alpha = self._agg(g, h, scores, c.bias.data, float(c.negative_slope) if self.gat else 0.0)
+        return y, scores, alpha
+
+    def _layer_bwd(self, k, g, h, scores, alpha, dy):
+        """conv k's backward from dy -> dL/dh; GAT's attention-vector gradients go into their buffers."""
+        c = self.convs[k]
+        if not self.gat:
+            return self._agg_bwd(g, h, None, None, dy, 0.0, None)
+        return self._agg_bwd(g, h, scores, alpha, dy, float(c.negative_slope), self._att(c),
+                             att_grads=(self._grad(c.att_src), self._grad(c.att_dst)))
+
+    # ---------------------------------------------------------------------------------------------- one batch
+    @torch.no_grad()
+    def step(self, nodes, loss_slot):
+        """One batch on `nodes`; loss_slot (one fp32 element on the device) receives the batch's BCE loss, NaN for a batch
+        without decoded edges (the loop's mean over nothing), whose gradients are zero and whose Adam step still runs."""
+        from .backbone import col_sum
+        from .framework.trainer import sampler as S
+        L, dev = _lib.lib(), self.dev
+        self._mark('start')
+        c = self.cut
+        cnt = c.cut(nodes)
+        n_b, e_b = cnt[0], cnt[1]
+        self._mark('cut')
+        g = c.batch_csr(False, self.gat)
+        self._mark('csr')
+        c1, c2 = self.convs
+        w1, w2, H, O = self.w1.data, self.w2.data, self.H, self.O
+        t1 = ops.rows_gather_gemm(self.x, c.nodes, w1)
+        p1, sc1, al1 = self._layer(0, g, t1)
+        t2 = ops.rows_gemm(p1, None, w2, trans_w=True, relu_in=True)
+        z, sc2, al2 = self._layer(1, g, t2)
+        self.z = z
+        self._mark('forward')
+        edges = c.e_index[:, :e_b]
+        neg = S.negative_sampling(edges, n_b, e_b).to(dev, torch.int64)
+        m_all = e_b + int(neg.shape[1])
+        self._mark('negatives')
+        if m_all == 0:
+            loss_slot.fill_(float('nan'))
+            for p in self.params:
+                self._grad(p).zero_()
+            self._mark('loss')
+        else:
+            dec = torch.cat([edges, neg], 1)                            # [2, M] contiguous: [batch edges | negatives]
+            inc_ptr = torch.empty(n_b + 1, dtype=torch.int64, device=dev)
+            other = torch.empty(2 * m_all, dtype=torch.int32, device=dev)
+            src_edge = torch.empty(2 * m_all, dtype=torch.int32, device=dev)
+            inc_ws = self._ws('incidence', L.gd_edge_incidence_workspace(n_b, m_all))
+            check(L.gd_edge_incidence(ptr(dec[0]), ptr(dec[1]), m_all, n_b, ptr(inc_ptr), ptr(other), ptr(src_edge), ptr(inc_ws),
+                                      inc_ws.numel(), stream_ptr(dev)), 'gd_edge_incidence')
+            w = torch.empty(m_all, dtype=torch.float32, device=dev)
+            w_inc = torch.empty(2 * m_all, dtype=torch.float32, device=dev)
+            bce_ws = self._ws('bce', 4 * max(1, L.gd_edge_bce_workspace(m_all, O)))
+            check(L.gd_edge_bce_f32(ptr(z), z.stride(0), n_b, O, ptr(dec), m_all, e_b, dec.data_ptr() + 8 * e_b, m_all,
+                                    m_all - e_b, 1.0, ptr(w), ptr(loss_slot), ptr(src_edge), ptr(inc_ptr), ptr(w_inc),
+                                    ptr(bce_ws), stream_ptr(dev)), 'gd_edge_bce_f32')
+            gz = torch.empty(n_b, O, dtype=torch.float32, device=dev)
+            check(L.gd_edge_dot_bwd_f32(ptr(z), z.stride(0), O, ptr(other), ptr(w_inc), None, 0, None, ptr(inc_ptr), n_b,
+                                        ptr(gz), gz.stride(0), stream_ptr(dev)), 'gd_edge_dot_bwd_f32')
+            self._mark('loss')
+            # BackboneEngine's backward on the batch: db2, layer 2 to its input, dW2, the ReLU gate with db1, layer 1, dW1
+            col_sum(gz, out=self._grad(c2.bias))
+            q2 = self._layer_bwd(1, g, t2, sc2, al2, gz)
+            ops.rows_gemm_wgrad(q2, None, p1, None, n_b, relu_mask=p1, out=self._grad(self.w2))
+            dx1 = ops.rows_gemm(q2, None, w2)
+            col_sum(dx1, gate=p1, gated=dx1, out=self._grad(c1.bias))                   # dp1 in place, db1
+            q1 = self._layer_bwd(0, g, t1, sc1, al1, dx1)
+            ops.rows_gemm_wgrad(q1, None, self.x, c.nodes.to(torch.int32), n_b, out=self._grad(self.w1))
+        for st, p in zip(self.adam, self.params):
+            check(L.gd_adam_f32(ptr(p.data), ptr(self._grad(p)), ptr(st['m']), ptr(st['v']), ptr(st['step']), p.numel(), self.lr,
+                                self.betas[0], self.betas[1], self.eps, stream_ptr(dev)), 'gd_adam_f32')
+            st['steps'] += 1
+        self._mark('backward')
+
+    # ---------------------------------------------------------------------------------------------- optimizer state
+    def import_adam_state(self, optimizer):
+        for st, p in zip(self.adam, self.params):
+            have = optimizer.state.get(p)
+            if have and 'exp_avg' in have:
+                st['m'].copy_(have['exp_avg'])
+                st['v'].copy_(have['exp_avg_sq'])
+                st['steps'] = int(have['step'])
+                st['step'].fill_(st['steps'])
+
+    def export_adam_state(self, optimizer):
+        """Adam moments and step count of every parameter into the caller's optimizer; no gradient is kept (the loop's
+        zero_grad after the step)."""
+        for st, p in zip(self.adam, self.params):
+            if st['steps']:
+                optimizer.state[p] = {'step': torch.tensor(float(st['steps'])), 'exp_avg': st['m'].clone(),
+                                      'exp_avg_sq': st['v'].clone()}
+            p.grad = None
+
+
+def train_minibatch_backbone_fused(trainer, model, data, optimizer, args, step_hook=None):
+    """Trainer.train_minibatch with the batch step on the HIP kernels: same sampler and negatives (same random stream), same
+    step and epoch records (the losses are read once per epoch), validation, best-validation-loss checkpoint, final
+    checkpoint and optimizer state."""
+    import time
+    from .framework.trainer import sampler as S
+    from .framework.trainer._log import wandb_log
+    from .framework.trainer.base import _require_gpu, device
+    from .framework.trainer.gnndelete_nodeemb import _adam_hyper
+    _require_gpu()
+    start = time.time()
+    best_valid_loss, best_epoch = 1000000, 0
+    model = model.to(device)
+    data = data.to('cpu')
+    data.edge_index = data.train_pos_edge_index
+    loader = S.make_sampler(data, args.batch_size, args.num_steps)
+    lr, betas, eps = _adam_hyper(optimizer)
+    step = MinibatchBackboneStep(model, data, loader, lr, betas, eps,
+                                 max_nodes=(loader.walk_length + 1) * max(int(loader.batch_size), 1))
+    step.import_adam_state(optimizer)
+    trainer._fused_minibatch_step = step
+    trainer.trainer_log['steps'] = []
+    for epoch in range(args.epochs):
+        model.train()
+        hist = torch.zeros(max(len(loader), 1), dtype=torch.float32, device=device)
+        done = 0
+        for i, nodes in enumerate(loader.node_sets()):
+            if i >= hist.shape[0]:
+                hist = torch.cat([hist, torch.zeros_like(hist)])
+            step.step(nodes, hist[i:i + 1])
+            done += 1
+            if step_hook is not None:
+                step_hook(step)
+        epoch_loss = 0.0
+        for i, loss in enumerate(hist[:done].tolist()):                  # the epoch's host read
+            rec = {'epoch': epoch, 'step': i, 'train_loss': loss}
+            wandb_log(rec)
+            trainer.trainer_log['steps'].append(rec)
+            epoch_loss += loss
+        if (epoch + 1) % args.valid_freq == 0:
+            step.export_adam_state(optimizer)               # (a checkpoint below carries the optimizer's state)
+            valid_loss, *_, valid_log = trainer.eval(model, data, 'val')
+            trainer._record({'epoch': epoch, 'train_loss': epoch_loss / max(done - 1, 1)}, valid_log)
+            if valid_loss < best_valid_loss:
+                best_valid_loss, best_epoch = valid_loss, epoch
+                print(f'Save best checkpoint at epoch {epoch:04d}. Valid loss = {valid_loss:.4f}')
+                torch.save({'model_state': model.state_dict(), 'optimizer_state': optimizer.state_dict()},
+                           os.path.join(args.checkpoint_dir, 'model_best.pt'))
+                torch.save(step.z.detach(), os.path.join(args.checkpoint_dir, 'node_embeddings.pt'))
+            data = data.to('cpu')
+    step.export_adam_state(optimizer)
+    trainer.trainer_log['training_time'] = time.time() - start
+    torch.save({'model_state': model.state_dict(), 'optimizer_state': optimizer.state_dict()},
+               os.path.join(args.checkpoint_dir, 'model_final.pt'))
+    trainer.trainer_log['best_epoch'], trainer.trainer_log['best_valid_loss'] = best_epoch, best_valid_loss

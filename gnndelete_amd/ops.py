@@ -213,6 +213,25 @@ def rows_gemm(inp, idx, w, trans_w=False, bias=None, relu_in=False, out=None, sa
     return out
 
 
+def rows_gather_gemm(x, idx, w, bias=None, relu_in=False, out=None):
+    """out[s] = act(x[idx[s]]) @ w^T (+ bias) into a compact [len(idx), d_out] matrix - raw call (gd_rows_gather_gemm_f32).
+    w: [d_out, d_in] (a Linear weight); idx: int64, may repeat, need not be sorted; an id outside x gives zeros (+ bias)."""
+    x = _f32_rows(x)
+    if idx.dtype != torch.int64 or idx.device != x.device:
+        raise TypeError('rows_gather_gemm: idx must be an int64 tensor on the device of x')
+    idx = idx.contiguous()
+    n_sel, d_in, d_out = int(idx.numel()), int(x.shape[1]), int(w.shape[0])
+    assert w.shape[1] == d_in
+    if out is None:
+        out = torch.empty(n_sel, d_out, dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= n_sel and out.shape[1] == d_out
+    w = w.contiguous()
+    check(_lib.lib().gd_rows_gather_gemm_f32(ptr(x), x.stride(0), x.shape[0], ptr(idx), n_sel, ptr(w), d_in, d_out, ptr(bias),
+                                             int(relu_in), ptr(out), out.stride(0), stream_ptr(x.device)),
+          'gd_rows_gather_gemm_f32')
+    return out
+
+
 def gate_rows(src, idx, sign_bits, out):
     """out[idx[s], :] = src[idx[s], :] where bit c of sign_bits[s] is set, else 0 (ReLU backward from the packed
     [z > 0] pattern the Del-1 kernel emitted): gd_gate_rows_f32, one launch on static buffers (graph-capturable)."""

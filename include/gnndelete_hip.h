@@ -416,6 +416,20 @@ int gd_rows_gemm_f32(const float* in, int64_t ld_in, const int32_t* idx, int32_t
                      const float* bias, int32_t relu_in,
                      float* out, int64_t ld_out, float* save_in, void* stream);
 
+/* The gathering form of gd_rows_gemm_f32 with trans_w = 1:
+ *   for s in [0,n_sel):  out[s,:] = act( in[idx[s],:] ) @ W^T (+ bias)       W is [d_out, d_in], `in` has n_in rows
+ * out is COMPACT ([n_sel, d_out], pitch ld_out); idx is int64 (a batch's node list), may repeat ids and need not be sorted.
+ * An id outside [0, n_in) reads nothing of `in` and gives a row of zeros (plus the bias).  This is layer 1 of a model
+ * that trains on GraphSAINT batches: x[nodes] W1^T with the current W1, without a gathered copy of x.
+ * The LDS-operand kernel of gd_rows_gemm_f32 under another row map (matrix-core forms and the scalar kernel for odd
+ * widths alike, never the weight-stationary form): the result equals, bit for bit, what that kernel gives on the
+ * gathered copy of the rows.  One launch; nothing beyond column d_out or row n_sel of out is written.
+ * n_sel == 0: GD_OK, no launch.  in == out: GD_E_DIM (rows are read while other rows are written).  n_in above 2^31 - 1,
+ * or no row at all with n_sel > 0: GD_E_DIM.  Widths and pitches: those of gd_rows_gemm_f32. */
+int gd_rows_gather_gemm_f32(const float* in, int64_t ld_in, int64_t n_in, const int64_t* idx, int32_t n_sel,
+                            const float* w, int32_t d_in, int32_t d_out, const float* bias, int32_t relu_in,
+                            float* out, int64_t ld_out, void* stream);
+
 /* gd_rows_gemm_f32 over a matrix whose rows live in two buffers of the same shape: row r is read from
  * in_alt where sel[r] != 0 and from in otherwise (e.g. z1 = Del-1 output on the S_Df rows, conv1 output
  * elsewhere: deletion.py:17-29 clones the whole matrix to get this; here neither copy is made). */
