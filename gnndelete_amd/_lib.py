@@ -39,6 +39,9 @@ PROTOTYPES = {
     'gd_rowpair_loss_f32': (ctypes.c_int, [_i32, _p, _i64, _p, _p, _i64, _p, _i32, _i32, _p, _p, _i64, _p]),
     'gd_random_walk': (ctypes.c_int, [_p, _p, _i32, _p, _i32, _i32, ctypes.c_uint64, _p, _p]),
     'gd_negative_edges': (ctypes.c_int, [_p, _i64, _i64, ctypes.c_uint64, _p, _i64, _p, _i64, _p]),
+    'gd_rank_counts_f32': (ctypes.c_int, [_p, _i64, _p, _i64, _p, _p, _p]),
+    'gd_subset_rank_workspace': (_i64, [_i64, _i64]),
+    'gd_subset_rank_metrics': (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _p]),
     'gd_rgcn_tile_kl': (ctypes.c_int32, [_i32, _i32, _i32, _i32]),
     'gd_rgcn_pack_weight_f32': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     'gd_rgcn_wave_covers': (ctypes.c_int32, [_i32, _i32, _i32]),

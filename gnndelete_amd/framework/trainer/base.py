@@ -17,6 +17,7 @@ from sklearn.metrics import accuracy_score, f1_score
 
 from ..evaluation import verification_error
 from ..graph_utils import negative_sampling
+from ...rankeval import fused_eval_unsupported, subset_auc_ap      # (--fused_eval; imports numpy and torch only)
 from ..metrics import batched_average_precision, batched_roc_auc
 from ..training_args import is_large
 from ..utils import get_link_labels
@@ -259,6 +260,19 @@ class Trainer:
         self._df_subset_index = torch.stack([torch.randperm(n_dr, device=dev, generator=gen)[:k] for _ in range(500)])
         self.df_pos_edge = [None] * 500          # placeholders: only the count is used on this path
 
+    # ------------------------------------------------------------------ --fused_eval (gnndelete_amd/rankeval.py)
+    def _fused_eval_applies(self, n_ref, m, k, scores):
+        """Does this ranking (n_ref negatives against k-subsets of m positives, `scores` one of the score tensors) run on the
+        rank kernels?  With the flag, trainer_log['eval_path'] says 'fused' or 'torch: <reason>'."""
+        if not getattr(self.args, 'fused_eval', False):
+            return False
+        reason = fused_eval_unsupported(n_ref, m, k, scores.is_cuda, scores.dtype)
+        path = 'fused' if reason is None else f'torch: {reason}'
+        if reason is not None and self.trainer_log.get('eval_path') != path:
+            print(f'--fused_eval: {reason}; ranking with the batched torch sort', flush=True)
+        self.trainer_log['eval_path'] = path
+        return reason is None
+
     @torch.no_grad()
     def eval(self, model, data, stage='val', pred_all=False):
         _require_gpu()
@@ -272,16 +286,37 @@ class Trainer:
         label = self.get_link_labels(pos_edge_index, neg_edge_index)
 
         loss = F.binary_cross_entropy_with_logits(logits, label).cpu().item()
-        # tensor AUC / AP (metrics.py): identical to scikit-learn's values, no host round trip
-        dt_auc = float(batched_roc_auc(logits, label)[0])
-        dt_aup = float(batched_average_precision(logits, label)[0])
+        n_pos = pos_edge_index.shape[1]
+        fused = self._fused_eval_applies(logits.numel() - n_pos, n_pos, n_pos, logits)
+        if fused:
+            # --fused_eval (gnndelete_amd/rankeval.py): the stage's negatives against ALL its positives, one subset
+            auc, aup = subset_auc_ap(logits[n_pos:], logits[:n_pos], torch.arange(n_pos, device=logits.device)[None])
+            dt_auc, dt_aup = float(auc[0]), float(aup[0])
+        else:
+            # tensor AUC / AP (metrics.py): identical to scikit-learn's values, no host round trip
+            dt_auc = float(batched_roc_auc(logits, label)[0])
+            dt_aup = float(batched_average_precision(logits, label)[0])
 
         if self.args.unlearning_model in ['original']:
             df_logit = []
+        elif fused:
+            df_score = model.decode(z, data.directed_df_edge_index).sigmoid()        # stays on the device for the ranking
+            df_logit = df_score.tolist()
         else:
             df_logit = model.decode(z, data.directed_df_edge_index).sigmoid().tolist()
 
-        if len(df_logit) > 0:
+        if len(df_logit) > 0 and fused:
+            dr_edges = data.train_pos_edge_index[:, data.dr_mask]
+            self._ensure_df_subsets(dr_edges.shape[1], len(df_logit), z.device)
+            dr_score = model.decode(z, dr_edges).sigmoid()
+            if getattr(self, '_df_subset_index', None) is None or self._df_subset_index.device != dr_score.device:
+                self._df_subset_index = torch.stack([c.nonzero().flatten() for c in self.df_pos_edge]).to(dr_score.device)
+            fused = self._fused_eval_applies(df_score.numel(), dr_score.numel(), self._df_subset_index.shape[1], dr_score)
+        if len(df_logit) > 0 and fused:
+            # the 500 resampled AUC / AUP from ONE sort of the Dr scores and a bitmap pass per subset: Df labelled 0, Dr labelled 1
+            auc, aup = subset_auc_ap(df_score, dr_score, self._df_subset_index)
+            df_auc, df_aup = float(auc.mean()), float(aup.mean())
+        elif len(df_logit) > 0:
             dr_edges = data.train_pos_edge_index[:, data.dr_mask]
             self._ensure_df_subsets(dr_edges.shape[1], len(df_logit), z.device)
             # one decode over all of Dr instead of 500 decodes of subsets (same scores), then the 500

@@ -54,7 +54,9 @@ extern "C" {
                                 gd_edge_incidence_fixed, gd_edge_incidence_update (+ their size queries): the incidence list when only
                                 the tail of the decoded edges changes (entries added: the version stays);
                                 gd_edgeprob_batch_loss_f32 (+ its _workspace query): the loss stage of the edge-probability GraphSAINT
-                                batch step (entries added: the version stays) */
+                                batch step (entries added: the version stays);
+                                gd_rank_counts_f32, gd_subset_rank_metrics (+ its _workspace query): resampled AUC / AP without the
+                                batched sort (entries added: the version stays) */
 
 enum {
   GD_OK = 0,
@@ -384,6 +386,33 @@ int gd_random_walk(const int32_t* rowptr, const int32_t* col, int32_t n_nodes, c
  * gnndelete_amd/negatives.reference_draw restates the stream on the CPU bit for bit. */
 int gd_negative_edges(const int64_t* pos_keys, int64_t n_keys, int64_t n_nodes, uint64_t seed, const int64_t* counter,
                       int64_t n_out, int64_t* out, int64_t ld_out, void* stream);
+
+/* Resampled ROC-AUC / average precision without a [B, 2k] sort (csrc/rankeval.hip; gnndelete_amd/rankeval.py holds the wrapper
+ * and the numpy restatement).  Every subset ranks the same n_ref negatives (`ref`, label 0) against k positives taken from one
+ * pool of m scores (label 1) through a row of pool indices that are DISTINCT WITHIN THE ROW.
+ *
+ * gd_rank_counts_f32: for each of m query scores, less[i] = the number of ref scores below it and leq[i] = the number at or
+ * below it (numpy.searchsorted left / right) as int32; ref [n_ref] ASCENDING, 1 <= n_ref < 2^31, 0 <= m < 2^31 (GD_E_DIM
+ * otherwise).  Two bounded binary searches per thread; a NaN query gives 0 / 0.  m == 0: GD_OK, no launch.
+ *
+ * gd_subset_rank_metrics: with the pool sorted DESCENDING, by sorted position p (int32 [m] each):
+ *     u2[p] = less + leq of the score at p,   ge_at[p] = n_ref - less,   run_end[p] = the last position with the same score
+ * and pos[e] = the sorted position of pool element e (int32 [m]); idx: int64, row b at idx + b * ld_idx, k indices in [0, m).
+ *     auc[b] = double(sum over the row of u2[pos[e]]) / (2 k n_ref)                         (int64 sum: exact)
+ *     ap[b]  = (1 / k) sum over the row's positions p of TP(p) / (TP(p) + ge_at[p]),  TP(p) = the row's members at positions
+ *              <= run_end[p]                                                                (float64)
+ * - sklearn's roc_auc_score (bit-equal to framework/metrics.batched_roc_auc) and average_precision_score (the recall step of a
+ * run of equal scores spread over the run's members: the last bits differ from a sum over thresholds).  auc, ap: float64
+ * [n_sub].  1 <= k <= m < 2^31, 1 <= n_ref < 2^30, 0 <= n_sub < 2^31, ld_idx >= k (GD_E_DIM otherwise); n_sub == 0: GD_OK, no
+ * launch.  workspace: gd_subset_rank_workspace(n_sub, m) BYTES (-1: sizes out of range), 16-byte aligned; its content on
+ * entry does not matter (each block zeroes its own rows: no memset call).  One launch, one block per subset; integer atomics
+ * only, fixed reduction order: the same bits on every call.  Indices outside [0, m) in idx, pos or run_end are skipped or
+ * clamped: a meaningless value, never an access outside the arrays. */
+int gd_rank_counts_f32(const float* ref, int64_t n_ref, const float* query, int64_t m, int32_t* less, int32_t* leq, void* stream);
+int64_t gd_subset_rank_workspace(int64_t n_sub, int64_t m);
+int gd_subset_rank_metrics(const int32_t* u2, const int32_t* ge_at, const int32_t* run_end, const int32_t* pos, const int64_t* idx,
+                           int64_t ld_idx, int64_t n_sub, int64_t k, int64_t m, int64_t n_ref, double* auc, double* ap,
+                           void* workspace, int64_t workspace_bytes, void* stream);
 
 /* The non-MSE row losses of the reference's loss zoo (framework/trainer/gnndelete_nodeemb.py:18-28), value per row
  * pair and gradient with respect to a, in one pass; rows of a / b optionally gathered through ia / ib (int64, NULL =
