@@ -107,6 +107,12 @@ PROTOTYPES = {
     'gd_del1_loss_wgrad_covers': (ctypes.c_int32, [_i32, _i32]),
     'gd_del1_loss_wgrad_parts': (ctypes.c_int32, [_i32]),
     'gd_del1_chain_loss_wgrad_f32': (ctypes.c_int, [_p, _i64, _p, _i32, _p, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _i32, _p]),
+    'gd_del1_chain_fold_covers': (ctypes.c_int32, [_i32, _i32, _i32]),
+    'gd_del1_chain_fold_loss_wgrad_f32': (ctypes.c_int, [_p, _i64, _p, _i32, _p, _p, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p,
+                                                         _p, _p, _i32, _p]),
+    'gd_layer1_fold_f32': (ctypes.c_int, [_p, _p, _p, _p, _p, _p]),
+    'gd_step_tail_fold1_f32': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p,
+                                              _f64, _f64, _f64, _f64, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p]),
     'gd_del1_loss_wgrad_f32': (ctypes.c_int, [_p, _i64, _p, _i32, _p, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _i32, _p]),
     'gd_rowtarget_mse_blocks': (_i32, [_i32]),
     'gd_rowfold_loss_blocks': (_i32, [_i32]),

@@ -733,13 +733,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // two waves of a pair, one wave per SIMD, partial matrices per block.
 // RANK1 (GATConv behind the gate): the formed gradient gets ra[row] ua[col] + rb[row] ub[col] added BEFORE the gate - the two
 // rank-1 terms of GAT's input gradient (d a_src (x) att_src W2 and d a_dst (x) att_dst W2; gd_rows_gemm_gated_rank1_f32's epilogue).
+// FOLD (the step with conv1's weight folded into W_D, F = H = 128): p = a = A^ x and w = W1^T W_D; the P1 accumulators of a unit start
+// from the folded bias row fo.bias (b1 W_D) at the lane's columns, so z, the sign bits and the loss terms see it; the partial matrices
+// are a^T g, written TRANSPOSED ([c][i]: the tail owns column strips), and the block's column sums 1^T g over its live rows go to
+// fo.colsum[slot][128] (same block order and zero filling as the partial matrices) - what b1^T (1^T g) of the weight gradient needs.
+// The g rows of a unit's clamped duplicates are zeroed in the tile (their p rows always were), so the sums skip them.
 struct ChainRank1 { const float* ra; const float* ua; const float* rb; const float* ub; };
-template <bool RANK1>
+struct ChainFold { const float* bias; float* colsum; };
+template <bool RANK1, bool FOLD = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void del1_chain_ws_kernel(
     const float* __restrict__ p, int64_t ld_p, const int32_t* __restrict__ idx, int32_t n_sel, const float* __restrict__ w,
     float* __restrict__ z, int64_t ld_z, uint32_t* __restrict__ sign_io, DelLoss loss, const float* __restrict__ dt, int64_t ld_dt,
-    const float* __restrict__ w_next, float* __restrict__ wg_partials, int32_t n_part, ChainRank1 r1) {
+    const float* __restrict__ w_next, float* __restrict__ wg_partials, int32_t n_part, ChainRank1 r1, ChainFold fo) {
   constexpr int D = 128, H = 64, PTP = 144, PTZ = 80;
+  constexpr int RT = D + 4;                                       // (FOLD) row pitch of the transposed block sums
   constexpr int kTiles = 4 * (16 * PTP + 16 * PTZ);               // floats of the four waves' transposition tiles
   extern __shared__ __attribute__((aligned(16))) float wl[];      // tiles | W_D image | W_next image; later 4 x D x H block sums
   __shared__ float lred[2][4];
@@ -792,6 +799,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   float4 x[8], dv[4], tv[4];
   float4 ua4[RANK1 ? 4 : 1], ub4[RANK1 ? 4 : 1];                    // (RANK1) this lane's columns of the two column vectors
   float ra_row = 0.f, rb_row = 0.f;                                 // (RANK1) this lane's row scalars
+  f32x4w bias4[FOLD ? 4 : 1];                                       // (FOLD) the folded bias at this lane's accumulator columns
+  float csum[FOLD ? 4 : 1];                                         // (FOLD) running column sums of g: column cb + 16 tb + r, rows kq mod 4
+  if (FOLD) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const float4 b4 = *reinterpret_cast<const float4*>(fo.bias + cb + 16 * t + 4 * kq);
+      bias4[t] = f32x4w{b4.x, b4.y, b4.z, b4.w};
+      csum[t] = 0.f;
+    }
+  }
   if (RANK1) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -852,7 +869,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int t = 0; t < 4; ++t) {
               const float4 wf = wq[i & 1][t];
               const float wa = c == 0 ? wf.x : c == 1 ? wf.y : c == 2 ? wf.z : wf.w;
-              if (i == 0 && c == 0) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa, xv[0], f32x4w{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+              if (i == 0 && c == 0) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa, xv[0], FOLD ? bias4[FOLD ? t : 0] : f32x4w{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
               else acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa, xv[c], acc[t], 0, 0, 0);
             }
         }
@@ -901,8 +918,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           dq.x = fmaf(rb_c, ub4[t].x, fmaf(ra_c, ua4[t].x, dq.x)); dq.y = fmaf(rb_c, ub4[t].y, fmaf(ra_c, ua4[t].y, dq.y));
           dq.z = fmaf(rb_c, ub4[t].z, fmaf(ra_c, ua4[t].z, dq.z)); dq.w = fmaf(rb_c, ub4[t].w, fmaf(ra_c, ua4[t].w, dq.w));
         }
-        const float4 gv = make_float4(cf * d4.x + ((m & 1u) ? dq.x : 0.f), cf * d4.y + ((m & 2u) ? dq.y : 0.f),
-                                      cf * d4.z + ((m & 4u) ? dq.z : 0.f), cf * d4.w + ((m & 8u) ? dq.w : 0.f));
+        float4 gv = make_float4(cf * d4.x + ((m & 1u) ? dq.x : 0.f), cf * d4.y + ((m & 2u) ? dq.y : 0.f),
+                                cf * d4.z + ((m & 4u) ? dq.z : 0.f), cf * d4.w + ((m & 8u) ? dq.w : 0.f));
+        if (FOLD) gv = make_float4(livef * gv.x, livef * gv.y, livef * gv.z, livef * gv.w);
         *reinterpret_cast<float4*>(tz + r * PTZ + 16 * t + 4 * kq) = gv;
       }
       sq *= livef;
@@ -926,6 +944,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int ta = 0; ta < 8; ++ta) a_op[ta] = tp[(4 * sp + kq) * PTP + 16 * ta + r];
 #pragma unroll
         for (int tb = 0; tb < 4; ++tb) b_op[tb] = tz[(4 * sp + kq) * PTZ + 16 * tb + r];
+        if (FOLD) {
+#pragma unroll
+          for (int tb = 0; tb < 4; ++tb) csum[tb] += b_op[tb];
+        }
 #pragma unroll
         for (int ta = 0; ta < 8; ++ta)
 #pragma unroll
@@ -939,20 +961,47 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
   // ---- block sum of the waves' D x H sums (pair order), loss sums
   __syncthreads();
-  float* const red = wl;                                          // [4][D x H]
+  float* const red = wl;                                          // [4][D x H]; FOLD: [4][H x RT] (column-major) | [4][H] column sums
+  if (FOLD) {
+    float* const cred = wl + 4 * H * RT;
 #pragma unroll
-  for (int ta = 0; ta < 8; ++ta)
+    for (int ta = 0; ta < 8; ++ta)
 #pragma unroll
-    for (int tb = 0; tb < 4; ++tb)
+      for (int tb = 0; tb < 4; ++tb)
+        *reinterpret_cast<float4*>(red + wave * H * RT + (16 * tb + r) * RT + 16 * ta + 4 * kq) =
+            make_float4(gacc[ta * 4 + tb][0], gacc[ta * 4 + tb][1], gacc[ta * 4 + tb][2], gacc[ta * 4 + tb][3]);
 #pragma unroll
-      for (int v = 0; v < 4; ++v) red[wave * D * H + (16 * ta + 4 * kq + v) * H + 16 * tb + r] = gacc[ta * 4 + tb][v];
-  __syncthreads();
-  for (int slot = blockIdx.x; slot < n_part; slot += gridDim.x) {
-    float* const out = wg_partials + (int64_t)slot * D * D;
-    const bool mine = slot == (int)blockIdx.x;
-    for (int e = tid; e < D * D; e += 256) {
-      const int i = e >> 7, c = e & 127, hf = c >> 6, ch = c & 63;
-      out[e] = mine ? red[hf * D * H + i * H + ch] + red[(2 + hf) * D * H + i * H + ch] : 0.f;
+    for (int tb = 0; tb < 4; ++tb) {
+      float cs = csum[FOLD ? tb : 0];
+      cs += __shfl_xor(cs, 16);
+      cs += __shfl_xor(cs, 32);
+      if (kq == 0) cred[wave * H + 16 * tb + r] = cs;
+    }
+    __syncthreads();
+    for (int slot = blockIdx.x; slot < n_part; slot += gridDim.x) {
+      float* const out = wg_partials + (int64_t)slot * D * D;       // [c][i]
+      const bool mine = slot == (int)blockIdx.x;
+      for (int e = tid; e < D * D; e += 256) {
+        const int c = e >> 7, i = e & 127, hf = c >> 6, ch = c & 63;
+        out[e] = mine ? red[hf * H * RT + ch * RT + i] + red[(2 + hf) * H * RT + ch * RT + i] : 0.f;
+      }
+      if (tid < D) fo.colsum[(int64_t)slot * D + tid] = mine ? cred[(tid >> 6) * H + (tid & 63)] + cred[(2 + (tid >> 6)) * H + (tid & 63)] : 0.f;
+    }
+  } else {
+#pragma unroll
+    for (int ta = 0; ta < 8; ++ta)
+#pragma unroll
+      for (int tb = 0; tb < 4; ++tb)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) red[wave * D * H + (16 * ta + 4 * kq + v) * H + 16 * tb + r] = gacc[ta * 4 + tb][v];
+    __syncthreads();
+    for (int slot = blockIdx.x; slot < n_part; slot += gridDim.x) {
+      float* const out = wg_partials + (int64_t)slot * D * D;
+      const bool mine = slot == (int)blockIdx.x;
+      for (int e = tid; e < D * D; e += 256) {
+        const int i = e >> 7, c = e & 127, hf = c >> 6, ch = c & 63;
+        out[e] = mine ? red[hf * D * H + i * H + ch] + red[(2 + hf) * D * H + i * H + ch] : 0.f;
+      }
     }
   }
   ls0 = wave_sum(ls0);
@@ -1193,12 +1242,43 @@ extern "C" int gd_del1_chain_loss_wgrad_f32(const float* p, int64_t ld_p, const 
     static const hipError_t at = hipFuncSetAttribute(reinterpret_cast<const void*>(&del1_chain_ws_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     if (at != hipSuccess) return fail(-(int)at, "%s: %s", name, hipGetErrorString(at));
     hipLaunchKernelGGL(del1_chain_ws_kernel<true>, dim3(grid), dim3(256), kLds, (hipStream_t)stream, p, ld_p, idx, n_sel, w, z, ld_z, sign_io, loss, dt,
-                       ld_dt, w_next, wgrad_partials, n_part, r1);
+                       ld_dt, w_next, wgrad_partials, n_part, r1, ChainFold{nullptr, nullptr});
   } else {
     static const hipError_t at = hipFuncSetAttribute(reinterpret_cast<const void*>(&del1_chain_ws_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     if (at != hipSuccess) return fail(-(int)at, "%s: %s", name, hipGetErrorString(at));
     hipLaunchKernelGGL(del1_chain_ws_kernel<false>, dim3(grid), dim3(256), kLds, (hipStream_t)stream, p, ld_p, idx, n_sel, w, z, ld_z, sign_io, loss, dt,
-                       ld_dt, w_next, wgrad_partials, n_part, r1);
+                       ld_dt, w_next, wgrad_partials, n_part, r1, ChainFold{nullptr, nullptr});
   }
   return launched("del1_chain_ws");
+}
+
+extern "C" int32_t gd_del1_chain_fold_covers(int32_t n_sel, int32_t d, int32_t h) {
+  return gd_del1_loss_wgrad_covers(n_sel, h) && d == 128 ? 1 : 0;
+}
+
+extern "C" int gd_del1_chain_fold_loss_wgrad_f32(const float* a, int64_t ld_a, const int32_t* idx, int32_t n_sel, const float* w_fold,
+                                                 const float* bias_fold, int32_t d, float* z, int64_t ld_z, uint32_t* sign_io,
+                                                 const int32_t* loss_slot, const float* tm, const float* coef, const float* cnt_signed,
+                                                 const float* dt, int64_t ld_dt, int32_t d_next, const float* w_next, float* loss_partials,
+                                                 float* wgrad_partials_t, float* colsum_partials, int32_t n_part, void* stream) {
+  using namespace gd;
+  const char* name = "gd_del1_chain_fold_loss_wgrad_f32";
+  if (n_sel == 0) return GD_OK;
+  GD_REQUIRE(a && idx && w_fold && bias_fold && z && sign_io && loss_slot && tm && coef && cnt_signed && dt && w_next && loss_partials &&
+                 wgrad_partials_t && colsum_partials, GD_E_NULL, "%s: null pointer", name);
+  GD_REQUIRE(d == 128 && d_next == 64, GD_E_DIM, "%s: widths %d / %d must be 128 / 64", name, d, d_next);
+  GD_REQUIRE(ld_a >= d && ld_z >= d && ld_dt >= d_next && ld_a % 4 == 0 && ld_z % 4 == 0 && ld_dt % 4 == 0, GD_E_DIM, "%s: bad row strides", name);
+  GD_REQUIRE(aligned16(a) && aligned16(z) && aligned16(tm) && aligned16(dt) && aligned16(wgrad_partials_t) && aligned16(bias_fold) &&
+                 (reinterpret_cast<uintptr_t>(sign_io) & 7u) == 0, GD_E_ALIGN, "%s: unaligned", name);
+  GD_REQUIRE(a != z && dt != z, GD_E_DIM, "%s: z must not alias a or dt", name);
+  GD_REQUIRE(n_part >= 1 && n_part <= gd_rows_gemm_wgrad_blocks(n_sel), GD_E_DIM,
+             "%s: n_part=%d outside [1, gd_rows_gemm_wgrad_blocks(n_sel)=%d]", name, n_part, gd_rows_gemm_wgrad_blocks(n_sel));
+  const DelLoss loss{loss_slot, tm, coef, cnt_signed, loss_partials};
+  const int grid = ws_cu_count() < n_part ? ws_cu_count() : n_part;
+  constexpr int kLds = (4 * (16 * 144 + 16 * 80) + 128 * 128 + 64 * 128) * 4;      // as the unfolded form (>= the 4 x 64 x 132 + 256 floats of its block sums)
+  static const hipError_t at = hipFuncSetAttribute(reinterpret_cast<const void*>(&del1_chain_ws_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+  if (at != hipSuccess) return fail(-(int)at, "%s: %s", name, hipGetErrorString(at));
+  hipLaunchKernelGGL((del1_chain_ws_kernel<false, true>), dim3(grid), dim3(256), kLds, (hipStream_t)stream, a, ld_a, idx, n_sel, w_fold, z, ld_z, sign_io, loss,
+                     dt, ld_dt, w_next, wgrad_partials_t, n_part, ChainRank1{nullptr, nullptr, nullptr, nullptr}, ChainFold{bias_fold, colsum_partials});
+  return launched("del1_chain_fold_ws");
 }

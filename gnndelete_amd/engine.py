@@ -31,6 +31,9 @@ consults, once per construction.  FORMS: plan_step(facts, knobs) - a pure functi
 calls - returns the StepForms the constructor then acts on in one pass (loss rows reordered, every buffer allocated once).
 One decision rides on top of the forms: plan_del2_fold(facts, forms, covers, enabled) - pure as well - says whether the chained
 GCN / GIN step folds W_D2 into conv2's weight (the Del-2 pass stores dz2 and W_D2^T W2 instead of forming dz2 W_D2^T per row).
+A second one of the same kind, plan_layer1_fold(facts, forms, covers, enabled): whether the chained GCN step folds conv1's weight
+into W_D1 - the step aggregates x itself (a = A^ x), the chained Del-1 pass takes a and W1^T W_D1, and a W1^T + b1 is formed only on
+the rows outside the Del-1 mask, the only rows whose conv1 output anything reads.
 """
 import os
 import warnings
@@ -170,6 +173,25 @@ def plan_del2_fold(facts, forms, covers, enabled=True):
     and where every layer-2 loss row is a Del row: a loss row outside takes the identity, and W_D2^T W2 would apply W_D2 to it.
     covers: gd_del_loss_fold_wgrad_covers(s2, o, h)."""
     return bool(enabled and covers and forms.chain1 and facts.mode in ('gcn', 'gin') and forms.fuse_wg2 and not forms.out2)
+
+
+def read_layer1_fold(env=None):
+    """GD_LAYER1_FOLD (default on; 0 = the unfolded step, for A/B runs).  Read once per construction; not a Knobs field, like
+    GD_DEL2_FOLD."""
+    env = os.environ if env is None else env
+    return env.get('GD_LAYER1_FOLD') != '0'
+
+
+def plan_layer1_fold(facts, forms, covers, enabled=True):
+    """Does the chained GCN step fold conv1's weight into W_D1?  Pure.  With a = A^ x, conv1's output is pre1 = a W1^T + 1 b1, and
+    on the Del-1 rows the layer-wise step reads it only linearly - z1[S1] = pre1[S1] W_D1 = a[S1] (W1^T W_D1) + b1 W_D1 and
+    dW_D1 = pre1[S1]^T g = W1 (a[S1]^T g) + b1^T (1^T g) - so x W1^T is formed on the rows OUTSIDE S1 only (the rows conv2 reads
+    un-Del'd).  Only where the chained pass runs out of place on a conv1 output recomputed every step (chain1, split1, no
+    cache_layer1), for GCNConv (aggregation and Linear commute, the bias comes last) with the layer-wise update (the chained pass
+    exists for it alone) at 128 hidden columns.  covers: gd_del1_chain_fold_covers(s1, x.shape[1], h) and conv1's weight is
+    128 x 128 - the input width is the engine's to check, StepFacts does not carry it."""
+    return bool(enabled and covers and forms.chain1 and forms.fuse_del1 and forms.split1 and facts.mode == 'gcn'
+                and facts.loss_type == 'both_layerwise' and not facts.cache_layer1 and facts.h == 128)
 
 
 def _loss_coefficients(loss_type, alpha):
@@ -720,6 +742,33 @@ class NodeembEngine:
         # _dt2_keep; zeros at the start (the first chained pass multiplies it by the zero dt2)
         self._fold2 = plan_del2_fold(self.facts, self.forms, lib.gd_del_loss_fold_wgrad_covers(self.s2, self.o, self.h), read_del2_fold())
         self._w2fold = torch.zeros(self.o, self.h, **f32) if self._fold2 else None
+        # _fold1 (plan_layer1_fold): conv1's Linear folded into W_D1.  _a1 = A^ x (every row, or the S2 rows of the rows-only step);
+        # _wf = W1^T W_D1 and _bf = b1 W_D1 are carried state like _w2fold - made here from the model's W_D1, then left by each tail
+        # launch for the next step; _cs1: the per-block column sums of the Del-1 gradient rows; _idx1c: the rows whose conv1 output
+        # conv2 reads as it is (outside S1; inside S2 where the step runs on the affected rows).  pre1 starts as zeros: its S1 rows
+        # are never written in this form and nothing may read them (the selector of the t2 product takes z1 there).
+        self._fold1 = False
+        if self._mode == 'gcn':
+            w1_ = conv1.lin.weight
+            self._fold1 = plan_layer1_fold(
+                self.facts, self.forms,
+                tuple(w1_.shape) == (128, 128) and x.shape[1] == 128 and x.dtype == torch.float32
+                and bool(lib.gd_del1_chain_fold_covers(self.s1, x.shape[1], self.h)), read_layer1_fold())
+        if self._fold1:
+            self._w1 = conv1.lin.weight.detach().float().contiguous()
+            self._b1 = (conv1.bias.detach().float().contiguous() if conv1.bias is not None else torch.zeros(self.h, **f32))
+            self._a1 = torch.zeros(n, self.h, **f32)
+            self._wf, self._bf = torch.empty(self.h, self.h, **f32), torch.empty(self.h, **f32)
+            check(lib.gd_layer1_fold_f32(ptr(self._w1), ptr(self._b1), ptr(self.wd1), ptr(self._wf), ptr(self._bf), stream_ptr(dev)),
+                  'gd_layer1_fold_f32')
+            self._cs1 = torch.zeros(max(1, lib.gd_rows_gemm_wgrad_blocks(self.s1)) * self.h, **f32)
+            rest = torch.ones(n, dtype=torch.bool, device=dev)
+            if self._rows_only:
+                rest.zero_()
+                rest[self.idx2.long()] = True
+            rest[self.idx1.long()] = False
+            self._idx1c = rest.nonzero().flatten().to(torch.int32)
+            self.pre1.zero_()
         self._gat_r1 = None                                           # (att_src W2, att_dst W2): constants of the frozen conv2
         if self._mode == 'gat':
             w2_ = conv2.lin_src.weight.detach()
@@ -843,6 +892,12 @@ class NodeembEngine:
         g = self.graph
         if self._mode == 'rgcn':
             self._rgcn_conv(c, self.x, self.pre1, 0)
+        elif self._mode == 'gcn' and self._fold1:
+            # a = A^ x (the rows-only step: on the S2 rows; x is complete, so no transformed buffer and no closure condition here),
+            # then conv1's output on the rows outside S1 alone
+            self._spmm(False, g.val, self.x, self._a1, None, 0.0, plan=self._plan2 if self._rows_only else None)
+            if self._idx1c.numel():
+                ops.rows_gemm(self._a1, self._idx1c, self._w1, trans_w=True, const_w=True, bias=self._b1, out=self.pre1)
         elif self._mode == 'gcn':
             idx, out, plan = self._layer1_rows(c.lin.weight)
             self._spmm(False, g.val, self._linear(self.x, c.lin.weight, idx=idx, out=out), self.pre1, c.bias, 0.0, plan=plan)
@@ -1025,6 +1080,7 @@ class NodeembEngine:
         """g1 (+)= xs1^T (dz1 + g_add) followed by Adam on W_D1.  With the fused form dz1 = coef (z1 - tbar)
         is formed inside the kernel's fetch from the folded layer-1 loss terms (no loss kernel, no dz1
         buffer traffic) and the layer-1 loss sums come out as per-block partials for the finalize kernel."""
+        assert not self._fold1, 'the folded layer-1 step never forms pre1 on the Del-1 rows: its weight gradient comes out of the chained pass'
         a1, a1_idx = (self.pre1, self.idx1) if self._split1 else (self.xs1, None)
         if not self._fuse_loss1:
             self._wgrad(a1, self.dz1, self.idx1, self.s1, self.g1, accumulate, self.ws1, adam=self.adam1,
@@ -1067,6 +1123,7 @@ class NodeembEngine:
             elif self._fuse_del1:
                 self._del1_fused(self.dh if lt == 'both_layerwise' else None)
             else:
+                assert not self._fold1
                 ops.rows_gemm(self.pre1, self.idx1, self.wd1, out=self.z1, save_in=self.xs1, sign_bits=self.z1_pos)
             fused_fin = self.t1.folded and self.t2.folded       # partials reduced by the finalize kernel
             if not fused_fin:
@@ -1122,13 +1179,22 @@ class NodeembEngine:
                 a1, a2 = self.adam1, self.adam2
                 lib_ = _lib.lib()
                 nw1 = self._lp1_blocks if self._fuse_del1 else lib_.gd_rows_gemm_wgrad_blocks(self.s1)      # partial matrices of W_D1
-                check(lib_.gd_step_tail_parts_f32(
-                    ptr(self.ws1), nw1, self.h, self._tail_acc[0], ptr(self.g1), ptr(a1.param), ptr(a1.m), ptr(a1.v),
-                    ptr(self.ws2), self._lp2_blocks if self._fuse_wg2 else lib_.gd_rows_gemm_wgrad_blocks(self.s2), self.o,
-                    self._tail_acc[1], ptr(self.g2), ptr(a2.param),
-                    ptr(a2.m), ptr(a2.v), a1.lr, a1.betas[0], a1.betas[1], a1.eps, ptr(p1), n1, ptr(p2), n2, ptr(self.hist),
-                    self.hist.shape[0], ptr(self.hist_pos), ptr(self.iter_ctr), ptr(self._arrive), stream_ptr(self.x.device)),
-                    'gd_step_tail_parts_f32')
+                if self._fold1:        # dW_D1 = W1 G + b1^T s from the transposed partials, Adam, and the next step's W1^T W_D1 / b1 W_D1
+                    check(lib_.gd_step_tail_fold1_f32(
+                        ptr(self.ws1), ptr(self._cs1), nw1, self.h, self._tail_acc[0], ptr(self._w1), ptr(self._b1), ptr(self.g1),
+                        ptr(a1.param), ptr(a1.m), ptr(a1.v), ptr(self._wf), ptr(self._bf),
+                        ptr(self.ws2), self._lp2_blocks if self._fuse_wg2 else lib_.gd_rows_gemm_wgrad_blocks(self.s2), self.o,
+                        self._tail_acc[1], ptr(self.g2), ptr(a2.param), ptr(a2.m), ptr(a2.v), a1.lr, a1.betas[0], a1.betas[1], a1.eps,
+                        ptr(p1), n1, ptr(p2), n2, ptr(self.hist), self.hist.shape[0], ptr(self.hist_pos), ptr(self.iter_ctr),
+                        ptr(self._arrive), stream_ptr(self.x.device)), 'gd_step_tail_fold1_f32')
+                else:
+                    check(lib_.gd_step_tail_parts_f32(
+                        ptr(self.ws1), nw1, self.h, self._tail_acc[0], ptr(self.g1), ptr(a1.param), ptr(a1.m), ptr(a1.v),
+                        ptr(self.ws2), self._lp2_blocks if self._fuse_wg2 else lib_.gd_rows_gemm_wgrad_blocks(self.s2), self.o,
+                        self._tail_acc[1], ptr(self.g2), ptr(a2.param),
+                        ptr(a2.m), ptr(a2.v), a1.lr, a1.betas[0], a1.betas[1], a1.eps, ptr(p1), n1, ptr(p2), n2, ptr(self.hist),
+                        self.hist.shape[0], ptr(self.hist_pos), ptr(self.iter_ctr), ptr(self._arrive), stream_ptr(self.x.device)),
+                        'gd_step_tail_parts_f32')
             else:
                 check(_lib.lib().gd_loss_finalize_f32(
                     ptr(p1) if fused_fin else None, n1 if fused_fin else 0,
@@ -1158,6 +1224,13 @@ class NodeembEngine:
                 if self._fold2:                # dt = A^T dz2 of the previous iteration; its W_D2^T W2 came out of that Del-2 pass
                     w_next = self._w2fold
                 rank1 = (None, None, None, None)
+            if self._fold1:                    # p = a, w = W1^T W_D1, accumulators from b1 W_D1; transposed partials + column sums
+                check(_lib.lib().gd_del1_chain_fold_loss_wgrad_f32(
+                    ptr(self._a1), self._a1.stride(0), ptr(self.idx1), self.s1, ptr(self._wf), ptr(self._bf), self.h, ptr(self.z1),
+                    self.z1.stride(0), ptr(self.z1_pos), ptr(self._slot1), ptr(self.t1.tm), ptr(self.t1.coef), ptr(self._cnt_signed1),
+                    ptr(dt), dt.stride(0), self.o, ptr(w_next), ptr(self._lp1), ptr(self.ws1), ptr(self._cs1), self._lp1_blocks,
+                    stream_ptr(self.x.device)), 'gd_del1_chain_fold_loss_wgrad_f32')
+                return
             check(_lib.lib().gd_del1_chain_loss_wgrad_f32(
                 ptr(self.pre1), self.pre1.stride(0), ptr(self.idx1), self.s1, ptr(self.wd1), self.h, ptr(self.z1), self.z1.stride(0),
                 ptr(self.z1_pos), ptr(self._slot1), ptr(self.t1.tm), ptr(self.t1.coef), ptr(self._cnt_signed1), ptr(dt),
@@ -1262,6 +1335,8 @@ class NodeembEngine:
                                       [self._gat_bufs[k] for k in ('dh', 'da_src', 'da_dst')])
         if self._fold2:
             state.append(self._w2fold)
+        if self._fold1:
+            state += [self._wf, self._bf]
         state.append(self._arrive)      # step_tail's check-in counter: a launch that did not finish must not leave it non-zero
         if self._user_wd2 is not None:                      # the caller's W_D2 behind a padded class dimension
             state.append(self._user_wd2.data)

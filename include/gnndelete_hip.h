@@ -673,6 +673,35 @@ int gd_del1_chain_loss_wgrad_f32(const float* p, int64_t ld_p, const int32_t* id
                                  const float* row_a, const float* col_a, const float* row_b, const float* col_b,
                                  float* loss_partials, float* wgrad_partials, int32_t n_part, void* stream);
 
+/* The chained pass of a step whose FIRST conv's Linear is folded into W_D (GCN, F = H = 128): with a = A^ x (the aggregated inputs,
+ * no bias), conv1's output is pre = a W1^T + 1 b1 and on the Del rows it is only read linearly, so
+ *     z[idx[s],:] = a[idx[s],:] @ w_fold + bias_fold          w_fold = W1^T W_D [128, 128], bias_fold = b1 W_D [128]
+ *     wgrad_partials_t[b][c][i] = block b's part of (a[idx,:]^T g)[i][c]      - TRANSPOSED [128][128] matrices
+ *     colsum_partials[b][c]     = block b's part of (1^T g)[c] over its n_sel rows (nothing from the padding of the last 16-row unit)
+ * so that dW_D = W1 (a^T g) + b1^T (1^T g) (gd_step_tail_fold1_f32 forms it).  g, sign_io, dt, w_next, the loss terms, the block
+ * order and the zero filling of the slots b < n_part behind the launch's blocks: as gd_del1_chain_loss_wgrad_f32 without the rank-1
+ * terms.  bias_fold 16-byte aligned; colsum_partials holds n_part * 128 floats.  gd_del1_chain_fold_covers(n_sel, d, h): 1 for
+ * d = h = 128 where gd_del1_loss_wgrad_covers(n_sel, h) holds. */
+int32_t gd_del1_chain_fold_covers(int32_t n_sel, int32_t d, int32_t h);
+int gd_del1_chain_fold_loss_wgrad_f32(const float* a, int64_t ld_a, const int32_t* idx, int32_t n_sel, const float* w_fold,
+                                      const float* bias_fold, int32_t d, float* z, int64_t ld_z, uint32_t* sign_io,
+                                      const int32_t* loss_slot, const float* tm, const float* coef, const float* cnt_signed,
+                                      const float* dt, int64_t ld_dt, int32_t d_next, const float* w_next, float* loss_partials,
+                                      float* wgrad_partials_t, float* colsum_partials, int32_t n_part, void* stream);
+/* w_fold = W1^T W_D and bias_fold = b1 W_D of that pass from scratch (W1 [128 out, 128 in] row-major, W_D [128, 128]); the
+ * arithmetic gd_step_tail_fold1_f32 uses for the next step's pair. */
+int gd_layer1_fold_f32(const float* w1, const float* b1, const float* wd, float* w_fold, float* bias_fold, void* stream);
+/* gd_step_tail_parts_f32 for that step.  Weight 2, the loss finalize and the check-in protocol are unchanged.  Weight 1 (d1 = 128,
+ * accumulate1 must be 0: GD_E_DIM otherwise) is finished per column c from the transposed partials and the column sums:
+ *     G[:, c] = sum_b partials1_t[b][c][:],  s[c] = sum_b colsum1[b][c]  (fixed orders);   dw1[:, c] = W1 G[:, c] + b1 s[c];
+ *     Adam on param1[:, c];   w_fold[:, c] = W1^T param1[:, c],  bias_fold[c] = b1 . param1[:, c]  from the UPDATED column. */
+int gd_step_tail_fold1_f32(const float* partials1_t, const float* colsum1, int32_t n_part1, int32_t d1, int32_t accumulate1,
+                           const float* w1, const float* b1, float* dw1, float* param1, float* exp_avg1, float* exp_avg_sq1,
+                           float* w_fold, float* bias_fold, const float* partials2, int32_t n_part2, int32_t d2, int32_t accumulate2,
+                           float* dw2, float* param2, float* exp_avg2, float* exp_avg_sq2, double lr, double beta1, double beta2,
+                           double eps, const float* loss_partials1, int32_t n1, const float* loss_partials2, int32_t n2,
+                           float* hist, int32_t capacity, int32_t* pos, int32_t* iter, int32_t* arrive, void* stream);
+
 /* ---------------------------------------------------------------- losses --------------- */
 
 /* Fused Deleted-Edge-Consistency + Neighborhood-Influence MSE terms of one layer, value and
