@@ -279,6 +279,12 @@ class Trainer:
         model.eval()
         model = model.to(device)        # --eval_on_cpu existed to dodge GPU OOM; not needed with 288 GB
         data = data.to(device)
+        if getattr(self.args, 'fused_validation', False):
+            # --fused_validation (gnndelete_amd/evalpass.py): the request's graph and edge lists prepared once, one scoring launch
+            from ... import evalpass
+            out = evalpass.prepared_link_validation(self, model, data, stage, pred_all, device)
+            if out is not None:
+                return out                  # (None: trainer_log['validation_path'] says why, and today's path runs)
         pos_edge_index = data[f'{stage}_pos_edge_index']
         neg_edge_index = data[f'{stage}_neg_edge_index']
         z = model(data.x, self._message_passing_edges(data))
@@ -430,6 +436,12 @@ class NodeClassificationTrainer(Trainer):
         model.eval()
         model = model.to(device)
         data = data.to(device)
+        if getattr(self.args, 'fused_validation', False):
+            # --fused_validation (gnndelete_amd/evalpass.py): the val_mask rows listed once, loss and hit count in one launch
+            from ... import evalpass
+            out = evalpass.prepared_node_validation(self, model, data, stage, device)
+            if out is not None:
+                return out
         z = F.log_softmax(model(data.x, data.edge_index), dim=1)
         sel = data.val_mask                       # upstream reads val_mask for every stage
         loss = F.nll_loss(z[sel], data.y[sel]).cpu().item()

@@ -453,25 +453,55 @@ def build_csr(edge_index, num_nodes, mode='gcn'):
 class _GraphCache:
     """Small identity-keyed cache: the trainer passes the same edge_index tensor every epoch.
     Entries hold a reference to the key tensor, so its storage cannot be recycled for a
-    different edge list while the entry is alive."""
+    different edge list while the entry is alive.
+
+    pin(edge_index) takes a tensor's graphs out of the LRU: they are built on first use as before, then held until
+    unpin(edge_index), however many other graphs pass through (the prepared validation pass, gnndelete_amd/evalpass.py, pins
+    its message-passing edges: a --minibatch trainer pushes a new graph through here every batch)."""
 
     def __init__(self, capacity=8):
         self.capacity = capacity
         self.entries = []
+        self.pins = {}                   # id(tensor) -> [tensor, pin count]
+        self.held = []                   # entries of pinned tensors, outside the LRU
 
     def get(self, edge_index, num_nodes, mode):
+        pinned = id(edge_index) in self.pins
+        for t, ver, n, m, g in (self.held if pinned else ()):
+            if t is edge_index and ver == edge_index._version and n == num_nodes and m == mode:
+                return g
         for i, (t, ver, n, m, g) in enumerate(self.entries):
             if t is edge_index and ver == edge_index._version and n == num_nodes and m == mode:
-                if i:
+                if pinned:                                          # (built before the pin: it moves out of the LRU)
+                    self.held.append(self.entries.pop(i))
+                elif i:
                     self.entries.insert(0, self.entries.pop(i))
                 return g
         g = build_csr(edge_index, num_nodes, mode)
+        if pinned:
+            # a graph of an earlier version of the tensor (edited in place since) will never be asked for again
+            self.held = [e for e in self.held if not (e[0] is edge_index and e[2] == num_nodes and e[3] == mode)]
+            self.held.append((edge_index, edge_index._version, num_nodes, mode, g))
+            return g
         self.entries.insert(0, (edge_index, edge_index._version, num_nodes, mode, g))
         del self.entries[self.capacity:]
         return g
 
+    def pin(self, edge_index):
+        self.pins.setdefault(id(edge_index), [edge_index, 0])[1] += 1
+
+    def unpin(self, edge_index):
+        pin = self.pins.get(id(edge_index))
+        if pin is None or pin[0] is not edge_index:
+            return
+        pin[1] -= 1
+        if pin[1] <= 0:
+            del self.pins[id(edge_index)]
+            self.held = [e for e in self.held if e[0] is not edge_index]
+
     def clear(self):
         self.entries.clear()
+        self.held.clear()
 
 
 CACHE = _GraphCache()

@@ -56,7 +56,9 @@ extern "C" {
                                 gd_edgeprob_batch_loss_f32 (+ its _workspace query): the loss stage of the edge-probability GraphSAINT
                                 batch step (entries added: the version stays);
                                 gd_rank_counts_f32, gd_subset_rank_metrics (+ its _workspace query): resampled AUC / AP without the
-                                batched sort (entries added: the version stays) */
+                                batched sort (entries added: the version stays);
+                                gd_eval_edge_scores_f32, gd_row_nll_eval_f32 (+ their _workspace queries): the per-validation scoring of
+                                the prepared validation pass (entries added: the version stays) */
 
 enum {
   GD_OK = 0,
@@ -981,6 +983,46 @@ int64_t gd_row_nll_workspace(int64_t n_sel, int32_t d);
 int gd_row_nll_f32(const float* z, int64_t ld_z, int64_t n_rows, int32_t d, int32_t d_valid, const int32_t* row_idx,
                    int64_t n_sel, const int64_t* y, float coef, float* dz, int64_t ld_dz, float* loss, float* workspace,
                    void* stream);
+
+/* ---------------------------------------------------------------- prepared validation --- */
+
+/* The per-validation scoring of the prepared link-prediction validation (gnndelete_amd/evalpass.py; Trainer.eval under
+ * --fused_validation, framework/trainer/base.py:229-300 upstream).  ONE decoded edge list (src[k], dst[k]), k < M, laid out
+ * [stage pos (n_pos) | stage neg (n_neg) | directed Df (n_df) | Dr (n_dr)], any segment may be empty, 1 <= M < 2^31:
+ *     scores[k] = sigmoid(<z[src[k], :d], z[dst[k], :d]>)      with e = exp(-|l|): l >= 0 ? 1 / (1 + e) : e / (1 + e); exactly 1.0f
+ *                                                              once e is below half an ulp of 1, never NaN for finite z
+ *     stats[0]  = (1 / (n_pos + n_neg)) sum over the stage's edges of  s (1 - y) + log1p(exp(-s)),   s = (double)scores[k],
+ *                 y = 1 for k < n_pos: binary_cross_entropy_with_logits applied to the SIGMOID OUTPUTS, as upstream does
+ *                 (base.py:243-247); NaN without stage edges
+ *     stats[1], stats[2] = mean and POPULATION standard deviation (np.mean / np.std) of the Df scores, in double, two passes
+ *                 (mean, then squared deviations); NaN for n_df = 0
+ *     status[0] = 1 when an endpoint lies outside [0, n_nodes), else 0: such an edge reads nothing outside z and scores logit 0
+ *                 (0.5); wrappers raise IndexError.  Written on every call (no zeroing by the caller).
+ * One lane group per edge, float4 loads, at most 1,024 blocks that walk the edges grid-strided, as gd_edge_bce_f32.  The loss
+ * terms are formed and added in double: per-block partials, added in block order by the one-block finishing launch, which also
+ * re-reads the Df scores in a fixed order (thread stride, then a fixed tree).  No atomics: the same bits on every call.
+ * d % 4 == 0, d <= 256, ld_z % 4 == 0 and >= d (GD_E_DIM), 16-byte aligned z, 8-byte aligned stats / workspace (GD_E_ALIGN).
+ * workspace: gd_eval_edge_scores_workspace(M, d) doubles.  Two launches, graph-capturable. */
+int64_t gd_eval_edge_scores_workspace(int64_t m_all, int32_t d);
+int gd_eval_edge_scores_f32(const float* z, int64_t ld_z, int64_t n_nodes, int32_t d, const int64_t* src, const int64_t* dst,
+                            int64_t n_pos, int64_t n_neg, int64_t n_df, int64_t n_dr, float* scores, double* stats,
+                            int32_t* status, double* workspace, void* stream);
+
+/* The per-validation scoring of the prepared node-classification validation (NodeClassificationTrainer.eval under
+ * --fused_validation, base.py:754-790 upstream) over the n_sel listed rows u = row_idx[i] (int32) of a pitched [n_rows, ld]
+ * matrix of d_valid classes, labels y indexed by node id (int64 [n_rows]):
+ *     loss[0]    = (1 / n_sel) sum_i ( logsumexp(z[u, :d_valid]) - z[u, y[u]] )        F.nll_loss(F.log_softmax(z, 1)[rows], y[rows])
+ *     correct[0] = the number of listed rows whose arg-max over [0, d_valid) equals y[u]
+ * The arg-max is the LOWEST index among equal maxima (torch.argmax / numpy.argmax on a row without NaN).  The row maximum is
+ * subtracted and the terms are formed in DOUBLE (exp / log / log1p in fp64; the label's term as log1p(sum_{j != y} e_j / e_y)
+ * while e_y is not tiny), per-block double partials added in block order, counts added as integers: the same bits every call.
+ * A row id outside [0, n_rows) is skipped and a label outside [0, d_valid) counts as wrong with term 0 (both still count in
+ * n_sel), as gd_row_nll_f32.  n_sel = 0 gives NaN and 0.  1 <= d_valid <= 256, ld >= d_valid, no alignment beyond the float
+ * (scalar loads); 8-byte aligned loss / correct / workspace.  workspace: gd_row_nll_eval_workspace(n_sel, d_valid) doubles.
+ * Two launches (one for n_sel = 0), graph-capturable. */
+int64_t gd_row_nll_eval_workspace(int64_t n_sel, int32_t d_valid);
+int gd_row_nll_eval_f32(const float* z, int64_t ld, int64_t n_rows, int32_t d_valid, const int32_t* row_idx, int64_t n_sel,
+                        const int64_t* y, double* loss, int64_t* correct, double* workspace, void* stream);
 
 /* ---------------------------------------------------------------- optimizer ------------ */
 
