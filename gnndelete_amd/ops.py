@@ -876,8 +876,9 @@ class _SegmentSoftmax(torch.autograd.Function):
     def forward(ctx, e, rowptr):
         e = e.contiguous().float()
         alpha = torch.zeros_like(e)
-        check(_lib.lib().gd_segment_softmax_f32(ptr(rowptr), ptr(e), int(rowptr.numel()) - 1, ptr(alpha), stream_ptr(e.device)),
-              'gd_segment_softmax_f32')
+        if e.numel():                   # (rows without a single entry: an empty tensor has no device pointer to hand over)
+            check(_lib.lib().gd_segment_softmax_f32(ptr(rowptr), ptr(e), int(rowptr.numel()) - 1, ptr(alpha), stream_ptr(e.device)),
+                  'gd_segment_softmax_f32')
         ctx.save_for_backward(alpha, rowptr)
         return alpha
 
@@ -886,8 +887,9 @@ class _SegmentSoftmax(torch.autograd.Function):
         alpha, rowptr = ctx.saved_tensors
         dalpha = dalpha.contiguous().float()
         de = torch.zeros_like(alpha)
-        check(_lib.lib().gd_segment_softmax_bwd_f32(ptr(rowptr), ptr(alpha), ptr(dalpha), int(rowptr.numel()) - 1, ptr(de),
-                                                    stream_ptr(alpha.device)), 'gd_segment_softmax_bwd_f32')
+        if alpha.numel():
+            check(_lib.lib().gd_segment_softmax_bwd_f32(ptr(rowptr), ptr(alpha), ptr(dalpha), int(rowptr.numel()) - 1, ptr(de),
+                                                        stream_ptr(alpha.device)), 'gd_segment_softmax_bwd_f32')
         return de, None
 
 
