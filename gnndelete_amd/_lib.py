@@ -142,6 +142,8 @@ PROTOTYPES = {
     'gd_row_nll_f32': (ctypes.c_int, [_p, _i64, _i64, _i32, _i32, _p, _i64, _p, _f32, _p, _i64, _p, _p, _p]),
     'gd_eval_edge_scores_workspace': (_i64, [_i64, _i32]),
     'gd_eval_edge_scores_f32': (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
+    'gd_eval_triple_scores_workspace': (_i64, [_i64, _i32]),
+    'gd_eval_triple_scores_f32': (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
     'gd_row_nll_eval_workspace': (_i64, [_i64, _i32]),
     'gd_row_nll_eval_f32': (ctypes.c_int, [_p, _i64, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p]),
     'gd_adam_at_f32': (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _f64, _f64, _f64, _f64, _p]),

@@ -3,7 +3,9 @@
 //
 //   gd_eval_edge_scores_f32   sigmoid(<z[a], z[b]>) of ONE decoded edge list [stage pos | stage neg | Df | Dr], the stage's
 //                             BCE-with-logits-on-sigmoid-outputs loss, and the mean / population std of the Df scores;
-//   gd_row_nll_eval_f32       mean NLL of log_softmax over the listed rows and the number of rows whose arg-max is the label.
+//   gd_row_nll_eval_f32       mean NLL of log_softmax over the listed rows and the number of rows whose arg-max is the label;
+//   gd_eval_triple_scores_f32 the knowledge-graph form (KGTrainer.eval, base.py:495-567): DistMult logits of ONE decoded triple
+//                             list, RAW for the stage (with its BCE-with-logits loss), sigmoid for Df / Dr, Df mean / std.
 //
 // What today's path does with three edge_dot launches, three sigmoids, a cat, a label tensor, a torch loss and numpy on a
 // host list (link prediction), or with two host copies and scikit-learn (node classification).  Both are streams followed by
@@ -75,6 +77,73 @@ __global__ __launch_bounds__(256) void eval_edge_scores_kernel(const float* __re
       if (k < n_stage) {
         const double sd = (double)s;
         sum += (k < n_pos ? 0.0 : sd) + log1p(exp(-sd));
+      }
+    }
+  }
+  sum = wave_sum_f64(sum);
+  bad = wave_sum_i32(bad);
+  if (lane == 0) {
+    red[wave] = sum;
+    bad_s[wave] = bad;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    flags[blockIdx.x] = (bad_s[0] | bad_s[1] | bad_s[2] | bad_s[3]) != 0;
+  }
+}
+
+// The knowledge-graph form of eval_edge_scores_kernel (KGTrainer.eval, base.py:495-567 upstream): one lane group per decoded
+// TRIPLE k < M, l_k = sum_j z[a_k, j] rel[t_k, j] z[b_k, j] with the product associated as edge_dot_kernel's DistMult decode
+// does ((z_a * rel) rounded, then an fma chain over z_b in the same lane / vector order).  An endpoint outside [0, n) or a type
+// outside [0, n_rel) reads nothing, scores l = 0 and raises the block's flag.  The stage's triples (k < n_stage) store the RAW
+// logit - upstream ranks and scores the stage without a sigmoid - and add, in double on the fp32 l widened,
+//     term = max(l, 0) - l y + log1p(exp(-|l|))        binary_cross_entropy_with_logits, finite at any finite l
+// the Df / Dr triples store sigmoid(l) by eval_edge_scores_kernel's two branches.
+template <int LPR>
+__global__ __launch_bounds__(256) void eval_triple_scores_kernel(const float* __restrict__ z, int64_t ld_z, int64_t n, int32_t d4,
+                                                                 const float* __restrict__ rel, int64_t ld_rel, int64_t n_rel,
+                                                                 const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
+                                                                 const int64_t* __restrict__ etype, int64_t n_pos, int64_t n_stage,
+                                                                 int64_t m_all, float* __restrict__ scores,
+                                                                 double* __restrict__ partials, int32_t* __restrict__ flags) {
+  constexpr int G = kWave / LPR;
+  __shared__ double red[4];
+  __shared__ int bad_s[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane / LPR, li = lane % LPR;
+  const int64_t per_pass = (int64_t)gridDim.x * 4 * G;
+  double sum = 0.0;
+  int bad = 0;
+  for (int64_t base = ((int64_t)blockIdx.x * 4 + wave) * G; base < m_all; base += per_pass) {
+    const int64_t k = base + g;
+    float l = 0.f;
+    if (k < m_all) {
+      const int64_t a = src[k], b = dst[k], t = etype[k];
+      if (a >= 0 && a < n && b >= 0 && b < n && t >= 0 && t < n_rel) {
+        const float4* x = reinterpret_cast<const float4*>(z + a * ld_z);
+        const float4* y = reinterpret_cast<const float4*>(z + b * ld_z);
+        const float4* r = reinterpret_cast<const float4*>(rel + t * ld_rel);
+        for (int vec = li; vec < d4; vec += LPR) {
+          float4 xv = x[vec];
+          const float4 yv = y[vec], rv = r[vec];
+          xv.x *= rv.x; xv.y *= rv.y; xv.z *= rv.z; xv.w *= rv.w;
+          l = fmaf(xv.x, yv.x, l); l = fmaf(xv.y, yv.y, l); l = fmaf(xv.z, yv.z, l); l = fmaf(xv.w, yv.w, l);
+        }
+      } else if (li == 0) {
+        bad = 1;
+      }
+    }
+#pragma unroll
+    for (int off = 1; off < LPR; off <<= 1) l += __shfl_xor(l, off);
+    if (k < m_all && li == 0) {
+      if (k < n_stage) {
+        scores[k] = l;
+        const double ld = (double)l;
+        sum += (ld > 0.0 ? ld : 0.0) - (k < n_pos ? ld : 0.0) + log1p(exp(-fabs(ld)));
+      } else {
+        const float e = expf(-fabsf(l));
+        scores[k] = l >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
       }
     }
   }
@@ -289,6 +358,51 @@ extern "C" int gd_eval_edge_scores_f32(const float* z, int64_t ld_z, int64_t n_n
   hipLaunchKernelGGL(eval_edge_scores_finish_kernel, dim3(1), dim3(kEvalFinishThreads), 0, s, workspace, flags, nb, n_stage,
                      scores + n_stage, n_df, stats, status);
   return launched("eval_edge_scores_finish");
+}
+
+extern "C" int64_t gd_eval_triple_scores_workspace(int64_t m_all, int32_t d) { return gd_eval_edge_scores_workspace(m_all, d); }
+
+extern "C" int gd_eval_triple_scores_f32(const float* z, int64_t ld_z, int64_t n_nodes, int32_t d, const float* rel, int64_t ld_rel,
+                                         int64_t n_rel, const int64_t* src, const int64_t* dst, const int64_t* etype, int64_t n_pos,
+                                         int64_t n_neg, int64_t n_df, int64_t n_dr, float* scores, double* stats, int32_t* status,
+                                         double* workspace, void* stream) {
+  using namespace gd;
+  GD_REQUIRE(n_pos >= 0 && n_neg >= 0 && n_df >= 0 && n_dr >= 0 && n_pos < (1ll << 31) && n_neg < (1ll << 31) && n_df < (1ll << 31) &&
+                 n_dr < (1ll << 31) && n_pos + n_neg + n_df + n_dr >= 1 && n_pos + n_neg + n_df + n_dr < (1ll << 31),
+             GD_E_DIM, "gd_eval_triple_scores_f32: segments %lld / %lld / %lld / %lld (non-negative, 1 <= their sum < 2^31)",
+             (long long)n_pos, (long long)n_neg, (long long)n_df, (long long)n_dr);
+  GD_REQUIRE(z && rel && src && dst && etype && scores && stats && status && workspace, GD_E_NULL,
+             "gd_eval_triple_scores_f32: null pointer");
+  GD_REQUIRE(n_nodes >= 1 && n_rel >= 1 && d > 0 && d % 4 == 0 && d <= 256 && ld_z >= d && ld_z % 4 == 0 && ld_rel >= d && ld_rel % 4 == 0,
+             GD_E_DIM, "gd_eval_triple_scores_f32: d=%d must be a multiple of 4 up to 256 with 16-byte row pitches (ld_z=%lld, ld_rel=%lld)",
+             d, (long long)ld_z, (long long)ld_rel);
+  GD_REQUIRE(aligned16(z) && aligned16(rel), GD_E_ALIGN, "gd_eval_triple_scores_f32: unaligned z / rel");
+  GD_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0 && (reinterpret_cast<uintptr_t>(stats) & 7u) == 0, GD_E_ALIGN,
+             "gd_eval_triple_scores_f32: stats / workspace must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n_stage = n_pos + n_neg, m_all = n_stage + n_df + n_dr;
+  const int d4 = d / 4;
+  const int lpr = lanes_per_row(d4);
+  const int nb = eval_blocks(m_all, lpr);
+  int32_t* flags = reinterpret_cast<int32_t*>(workspace + nb);
+#define GD_EVAL_CASE(LPR)                                                                                                             \
+  hipLaunchKernelGGL((eval_triple_scores_kernel<LPR>), dim3(nb), dim3(256), 0, s, z, ld_z, n_nodes, d4, rel, ld_rel, n_rel, src, dst, \
+                     etype, n_pos, n_stage, m_all, scores, workspace, flags)
+  switch (lpr) {
+    case 1: GD_EVAL_CASE(1); break;
+    case 2: GD_EVAL_CASE(2); break;
+    case 4: GD_EVAL_CASE(4); break;
+    case 8: GD_EVAL_CASE(8); break;
+    case 16: GD_EVAL_CASE(16); break;
+    case 32: GD_EVAL_CASE(32); break;
+    default: GD_EVAL_CASE(64); break;
+  }
+#undef GD_EVAL_CASE
+  int rc = launched("eval_triple_scores");
+  if (rc) return rc;
+  hipLaunchKernelGGL(eval_edge_scores_finish_kernel, dim3(1), dim3(kEvalFinishThreads), 0, s, workspace, flags, nb, n_stage,
+                     scores + n_stage, n_df, stats, status);
+  return launched("eval_triple_scores_finish");
 }
 
 extern "C" int64_t gd_row_nll_eval_workspace(int64_t n_sel, int32_t d_valid) {

@@ -22,7 +22,13 @@ saturated scores tie.  Given the kernel's scores, nothing else moves: the AUCs a
 them, the AUPs within 1e-12, loss / Df mean / Df std within 1e-12 of reference_edge_scores on them.  Values under the flag are
 therefore NOT promised bit-equal to the no-flag path; a near-tie in valid_loss can select a different best epoch.
 
-reference_edge_scores and reference_row_nll_eval restate the two entries in numpy (fp64 throughout) and are their CPU oracles."""
+reference_edge_scores and reference_row_nll_eval restate the two entries in numpy (fp64 throughout) and are their CPU oracles.
+
+KGTrainer.eval (R-GCN / R-GAT, DistMult) validates the same way on a KGValidationPlan: the Dr triples selected once and pinned
+in graph.TYPED (ONE typed graph for conv1 and conv2 instead of one each per validation), gd_eval_triple_scores_f32 over one
+decoded triple list (raw logits and BCE-with-logits for the stage, as upstream scores it; sigmoid for Df / Dr), the rank kernels
+for both rankings.  Its staleness check also compares contents, because the knowledge-graph loops move the data to the host
+between validations; its 500 Dr subsets stay upstream's fresh draws per call.  reference_triple_scores is that entry's oracle."""
 import numpy as np
 import torch
 
@@ -70,6 +76,42 @@ def reference_edge_scores(z, src, dst, segments, scores=None):
     if int(sum(int(v) for v in segments)) != s64.size:
         raise ValueError(f'reference_edge_scores: segments {tuple(segments)} do not add up to {s64.size} edges')
     return (s64,) + reference_edge_stats(s64.astype(np.float32) if scores is None else scores, segments)
+
+
+def reference_triple_stats(scores, segments):
+    """(loss, df_mean, df_std) of gd_eval_triple_scores_f32 from the scores [M] laid out by `segments` = (n_pos, n_neg, n_df,
+    n_dr), fp64.  The stage's scores are RAW logits l (KGTrainer.eval scores the stage without sigmoid): loss = the mean over
+    the stage of max(l, 0) - l y + log1p(exp(-|l|)), binary_cross_entropy_with_logits (NaN without stage triples); mean and
+    population std of the Df segment, which holds sigmoid outputs (NaN when it is empty)."""
+    n_pos, n_neg, n_df, _ = (int(v) for v in segments)
+    s = _np(scores).astype(np.float64).reshape(-1)
+    stage, y = s[:n_pos + n_neg], np.concatenate([np.ones(n_pos), np.zeros(n_neg)])
+    loss = float(np.mean(np.maximum(stage, 0.0) - stage * y + np.log1p(np.exp(-np.abs(stage))))) if stage.size else float('nan')
+    df = s[n_pos + n_neg:n_pos + n_neg + n_df]
+    if df.size == 0:
+        return loss, float('nan'), float('nan')
+    mean = float(np.mean(df))
+    return loss, mean, float(np.sqrt(np.mean((df - mean) ** 2)))
+
+
+def reference_triple_scores(z, rel, src, dst, etype, segments, scores=None):
+    """gd_eval_triple_scores_f32 on the CPU in numpy, fp64 throughout -> (scores64 [M], loss, df_mean, df_std).  scores64 = the
+    fp64 DistMult logits sum_j z[a, j] rel[t, j] z[b, j] for the stage's triples and their sigmoid for Df / Dr (an endpoint
+    outside [0, n) or a type outside [0, n_rel) scores logit 0).  The three statistics are defined on the fp32 values the kernel
+    stores: they are taken over `scores` when given (the kernel's output), else over scores64 rounded to float32."""
+    z, rel = _np(z).astype(np.float64), _np(rel).astype(np.float64)
+    src, dst, etype = (_np(t, np.int64).reshape(-1) for t in (src, dst, etype))
+    n, n_rel = z.shape[0], rel.shape[0]
+    ok = (src >= 0) & (src < n) & (dst >= 0) & (dst < n) & (etype >= 0) & (etype < n_rel)
+    a, b, t = np.where(ok, src, 0), np.where(ok, dst, 0), np.where(ok, etype, 0)
+    logit = np.where(ok, np.einsum('ij,ij,ij->i', z[a], rel[t], z[b]), 0.0)
+    if int(sum(int(v) for v in segments)) != logit.size:
+        raise ValueError(f'reference_triple_scores: segments {tuple(segments)} do not add up to {logit.size} triples')
+    e = np.exp(-np.abs(logit))
+    s64 = np.where(logit >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+    n_stage = int(segments[0]) + int(segments[1])
+    s64[:n_stage] = logit[:n_stage]
+    return (s64,) + reference_triple_stats(s64.astype(np.float32) if scores is None else scores, segments)
 
 
 def reference_row_nll_eval(z, rows, y, d_valid=None):
@@ -120,6 +162,40 @@ def eval_edge_scores(z, src, dst, segments, check=True, out=None):
                                            ptr(status), ptr(ws), stream_ptr(dev)), 'gd_eval_edge_scores_f32')
     if check and int(status):
         raise IndexError(f'eval_edge_scores: an edge has an endpoint outside [0, {n})')
+    return scores, stats, status
+
+
+def eval_triple_scores(z, rel, src, dst, etype, segments, check=True, out=None):
+    """gd_eval_triple_scores_f32 on device tensors -> (scores float32 [M], stats float64 [3] = loss / Df mean / Df std, status
+    int32 [1]).  z: float32 [n, d], rel: float32 [n_rel, d] (the DistMult table), d a multiple of 4 up to 256, rows 16-byte
+    aligned; src / dst / etype: int64 [M] laid out by `segments` = (n_pos, n_neg, n_df, n_dr).  The stage's scores are the raw
+    logits, the Df / Dr scores their sigmoid.  check=True reads the status (a host sync) and raises IndexError on an endpoint
+    outside [0, n) or a type outside [0, n_rel); out: as eval_edge_scores."""
+    from . import _lib
+    from ._lib import check as check_rc, ptr, stream_ptr
+    n_pos, n_neg, n_df, n_dr = (int(v) for v in segments)
+    if z.dim() != 2 or z.dtype != torch.float32 or not z.is_cuda or z.stride(1) != 1:
+        raise ValueError('eval_triple_scores: z must be a float32 matrix with contiguous rows on the GPU')
+    if rel.dim() != 2 or rel.dtype != torch.float32 or rel.device != z.device or rel.stride(1) != 1 or rel.shape[1] != z.shape[1]:
+        raise ValueError(f'eval_triple_scores: rel must be a float32 [n_rel, {z.shape[1]}] matrix with contiguous rows on the device of z')
+    for name, t in (('src', src), ('dst', dst), ('etype', etype)):
+        if t.dtype != torch.int64 or t.dim() != 1 or t.device != z.device or t.numel() != n_pos + n_neg + n_df + n_dr:
+            raise ValueError(f'eval_triple_scores: {name} must be int64 [{n_pos + n_neg + n_df + n_dr}] on the device of z')
+    src, dst, etype = src.contiguous(), dst.contiguous(), etype.contiguous()
+    dev, (n, d), m_all = z.device, z.shape, src.numel()
+    L = _lib.lib()
+    if out is not None and (out.dtype != torch.float32 or out.device != dev or out.dim() != 1 or out.numel() != m_all or not out.is_contiguous()):
+        raise ValueError(f'eval_triple_scores: out must be a contiguous float32 [{m_all}] on the device of z')
+    scores = torch.empty(m_all, dtype=torch.float32, device=dev) if out is None else out
+    stats = torch.empty(3, dtype=torch.float64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(2, int(L.gd_eval_triple_scores_workspace(m_all, d))), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check_rc(L.gd_eval_triple_scores_f32(ptr(z), z.stride(0), n, d, ptr(rel), rel.stride(0), rel.shape[0], ptr(src), ptr(dst), ptr(etype),
+                                             n_pos, n_neg, n_df, n_dr, ptr(scores), ptr(stats), ptr(status), ptr(ws), stream_ptr(dev)),
+                 'gd_eval_triple_scores_f32')
+    if check and int(status):
+        raise IndexError(f'eval_triple_scores: a triple has an endpoint outside [0, {n}) or a type outside [0, {rel.shape[0]})')
     return scores, stats, status
 
 
@@ -176,6 +252,28 @@ def validation_unsupported(model, task='linkpred', width=None, dtype=torch.float
             return f'embedding width {width} (a multiple of 4 up to {MAX_WIDTH})'
         if task == 'nodecls' and not 1 <= width <= MAX_WIDTH:
             return f'{width} classes (the scoring kernel takes up to {MAX_WIDTH})'
+    for n_ref, m, k in rankings:
+        reason = rankeval.fused_eval_unsupported(n_ref, m, k)
+        if reason is not None:
+            return reason
+    return None
+
+
+def kg_validation_unsupported(model, width=None, dtype=torch.float32, on_gpu=True, rankings=()):
+    """None when the prepared knowledge-graph validation takes this validation (KGTrainer.eval), else the reason (one line).
+    model: RGCN / RGAT or their Delete wrappers; width, dtype, on_gpu: of the embeddings of the model's forward and of its
+    DistMult table (width None: only the model and the rankings are looked at); rankings: as validation_unsupported."""
+    from .framework.models.backbones import RGCN
+    if not isinstance(model, RGCN):
+        return f'no prepared knowledge-graph validation for the {type(model).__name__} model (RGCN, RGAT and their Delete wrappers only)'
+    if width is not None:
+        width = int(width)
+        if not on_gpu:
+            return 'the embeddings or the DistMult table are not on the GPU'
+        if dtype != torch.float32:
+            return f'{dtype} embeddings or DistMult table (float32 only)'
+        if width % 4 or not 4 <= width <= MAX_WIDTH:
+            return f'DistMult width {width} (a multiple of 4 up to {MAX_WIDTH})'
     for n_ref, m, k in rankings:
         reason = rankeval.fused_eval_unsupported(n_ref, m, k)
         if reason is not None:
@@ -317,6 +415,137 @@ class NodeValidationPlan:
         return loss, dt_acc, dt_f1, log
 
 
+# ---------------------------------------------------------------------------------------------- knowledge graphs
+class KGValidationPlan:
+    """Everything of a knowledge-graph validation (KGTrainer.eval) that depends only on the request; one per (trainer, stage):
+    the Dr message-passing edges and types, selected ONCE and pinned in graph.TYPED (one typed graph for conv1 and conv2, held
+    while the batches' graphs pass through the convs), the decoded triple list [stage pos | stage neg | directed Df | Dr] with
+    its segments, and the stage's all-positives row.
+
+    The knowledge-graph loops move the data to the host between validations (data.to('cpu'), then eval's data.to(device)), so
+    every validation presents NEW tensors: the staleness check (current) first compares identity and _version of every source
+    as LinkValidationPlan does, and where that differs but shapes, dtypes and device agree it compares the CONTENTS exactly
+    against the sources the plan holds (elementwise equality reduced to one flag, one host read; no hash).  Equal contents adopt
+    the new tensors as the plan's sources and keep everything derived; anything else rebuilds.
+
+    The 500 Dr subsets are NOT the plan's: upstream draws them fresh on every call, and validate() makes the same generator
+    calls in the same order as KGTrainer.eval, so a seed gives the same subsets and leaves the same host random stream."""
+
+    N_SUBSETS = 500
+
+    @staticmethod
+    def sources(data, stage, original):
+        """The tensors the plan is derived from, in the order of its staleness key."""
+        dfdr = () if original else (data.directed_df_edge_index, data.directed_df_edge_type, data.train_pos_edge_index, data.train_edge_type)
+        return (data.edge_index, data.edge_type, data.dr_mask, data[f'{stage}_pos_edge_index'], data[f'{stage}_neg_edge_index'],
+                data[f'{stage}_edge_type']) + dfdr
+
+    @classmethod
+    def key_of(cls, data, stage, original, device):
+        return (stage, bool(original), str(device)) + _stamp(*cls.sources(data, stage, original))
+
+    def __init__(self, trainer, data, stage, device):
+        from . import graph
+        original = trainer.args.unlearning_model in ['original']
+        self.stage, self.original, self.device = stage, original, device
+        self.key = self.key_of(data, stage, original, device)
+        self._sources = self.sources(data, stage, original)          # held: what a later validation's tensors are compared with
+        edge_index, edge_type, dr_mask, pos, neg, etype = self._sources[:6]
+        self.edges = edge_index[:, dr_mask].contiguous()             # the message-passing triples, selected ONCE
+        self.types = edge_type[dr_mask].contiguous()
+        self._registry = graph.TYPED
+        self._registry.pin(self.edges, self.types)                   # their typed graph is built on first use and held, shared by the convs
+        self._pinned = True
+        parts, types = [pos, neg], [etype, etype]
+        if not original and data.directed_df_edge_index.shape[1] > 0:
+            df, df_type, train, train_type = self._sources[6:]
+            half = dr_mask[:dr_mask.shape[0] // 2]
+            parts += [df, train[:, half]]
+            types += [df_type, train_type[half]]
+        self.segments = tuple(int(p.shape[1]) for p in parts) + ((0, 0) if len(parts) == 2 else ())
+        decoded = torch.cat(parts, dim=1).long().contiguous()        # int64 [2, M]: [stage pos | stage neg | directed Df | Dr]
+        self.decoded, self.src, self.dst = decoded, decoded[0], decoded[1]
+        self.etype = torch.cat(types, dim=0).long().contiguous()
+        self.all_positives = torch.arange(self.segments[0], device=decoded.device)[None]
+        self.z = self.scores = self.subsets = None                   # of the latest validation
+
+    def current(self, data, stage, original, device):
+        """Is the plan still that of (data, stage)?  True on an identity hit, or after adopting tensors of equal contents."""
+        key = self.key_of(data, stage, original, device)
+        if key == self.key:
+            return True
+        if key[:3] != self.key[:3]:
+            return False
+        new, equal = self.sources(data, stage, original), []
+        for old, stamp, t in zip(self._sources, self.key[3:], new):
+            if old is t and stamp == (id(t), t._version):
+                continue
+            # an in-place edit (of the tensor presented, or of the one held) is not compared: the held values are no longer
+            # the ones the plan was derived from
+            if old is t or old._version != stamp[1] or t.shape != old.shape or t.dtype != old.dtype or t.device != old.device:
+                return False
+            equal.append((t == old).all())
+        if not bool(torch.stack(equal).all()):                       # ONE host read
+            return False
+        self._sources, self.key = new, key
+        return True
+
+    def rankings(self):
+        n_pos, n_neg, n_df, n_dr = self.segments
+        return [(n_neg, n_pos, n_pos)] + ([(n_df, n_dr, n_df)] if n_df > 0 else [])
+
+    def release(self):
+        if getattr(self, '_pinned', False):
+            self._pinned = False
+            self._registry.unpin(self.edges, self.types)
+
+    __del__ = LinkValidationPlan.__del__
+
+    def _draw_subsets(self, trainer, n_dr, k, dev):
+        """KGTrainer.eval's draws, call for call: 500 host permutations up to FAST_SUBSETS_ABOVE pool scores, beyond it one host
+        randint seeding 500 device permutations."""
+        if n_dr <= trainer.FAST_SUBSETS_ABOVE:
+            return torch.stack([torch.randperm(n_dr)[:k].sort().values for _ in range(self.N_SUBSETS)]).to(dev)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(torch.randint(0, 2 ** 31 - 1, (1,))))
+        picks = torch.empty(self.N_SUBSETS, k, dtype=torch.int64, device=dev)
+        for row in picks:                # the same draws, copied row by row: a list of [:k] views would hold all 500 permutations
+            row.copy_(torch.randperm(n_dr, device=dev, generator=gen)[:k])
+        return picks
+
+    @torch.no_grad()
+    def validate(self, trainer, model, data, pred_all=False, z=None):
+        """One validation -> KGTrainer.eval's tuple.  z: model(data.x, self.edges, self.types) when the caller has run it."""
+        from .framework.trainer.base import _all_pairs
+        stage = self.stage
+        n_pos, n_neg, n_df, n_dr = self.segments
+        n_stage = n_pos + n_neg
+        if z is None:
+            z = model(data.x, self.edges, self.types)
+        scores, stats, status = eval_triple_scores(z, model.W.detach(), self.src, self.dst, self.etype, self.segments, check=False)
+        self.z, self.scores = z, scores
+        auc, aup = rankeval.subset_auc_ap(scores[n_pos:n_stage], scores[:n_pos], self.all_positives)      # raw logits, as upstream
+        parts = [stats, status.double(), auc, aup]
+        if n_df > 0:
+            df_score = scores[n_stage:n_stage + n_df]
+            self.subsets = self._draw_subsets(trainer, n_dr, n_df, scores.device)
+            auc, aup = rankeval.subset_auc_ap(df_score, scores[n_stage + n_df:], self.subsets)
+            parts += [auc.mean()[None], aup.mean()[None]]
+        host = torch.cat(parts).tolist()                             # the validation's ONE read of its scalars
+        if host[3] != 0.0:
+            raise IndexError(f'--fused_validation: a triple of the {stage} validation has an endpoint outside [0, {z.shape[0]}) or a type '
+                             f'outside [0, {model.W.shape[0]})')
+        loss, dt_auc, dt_aup = host[0], host[4], host[5]
+        df_logit = df_score.tolist() if n_df > 0 else []
+        df_auc, df_aup = (host[6], host[7]) if n_df > 0 else (np.nan, np.nan)
+        logit_all_pair = _all_pairs(z) if pred_all else None
+        log = {f'{stage}_loss': loss, f'{stage}_dt_auc': dt_auc, f'{stage}_dt_aup': dt_aup, f'{stage}_df_auc': df_auc,
+               f'{stage}_df_aup': df_aup,
+               f'{stage}_df_logit_mean': host[1] if n_df > 0 else np.nan,
+               f'{stage}_df_logit_std': host[2] if n_df > 0 else np.nan}
+        return loss, dt_auc, dt_aup, df_auc, df_aup, df_logit, logit_all_pair, log
+
+
 # ---------------------------------------------------------------------------------------------- the trainers' entry
 def _fallback(trainer, reason):
     path = f'torch: {reason}'
@@ -351,6 +580,34 @@ def prepared_link_validation(trainer, model, data, stage, pred_all, device):
     if reason is not None:
         return _fallback(trainer, reason)
     out = plan.validate(model, data, pred_all, z)
+    trainer.trainer_log['validation_path'] = 'prepared'
+    return out
+
+
+def prepared_kg_validation(trainer, model, data, stage, pred_all, device):
+    """KGTrainer.eval under --fused_validation: its tuple, or None after recording why the torch path runs instead (model and
+    data are on `device`, the model in eval mode).  The model and the width of its DistMult table are looked at before anything
+    is built, and nothing is drawn from a generator before the last check: a fallback leaves the random stream to the torch
+    path, which then gives exactly its no-flag values."""
+    reason = kg_validation_unsupported(model)
+    if reason is None:
+        reason = kg_validation_unsupported(model, model.W.shape[1], model.W.dtype, model.W.is_cuda)
+    if reason is not None:
+        return _fallback(trainer, reason)
+    original = trainer.args.unlearning_model in ['original']
+    plans = trainer.__dict__.setdefault('_validation_plans', {})
+    plan = plans.get(('kg', stage))
+    if plan is None or not plan.current(data, stage, original, device):
+        if plan is not None:
+            plan.release()
+        plan = plans[('kg', stage)] = KGValidationPlan(trainer, data, stage, device)
+    z = model(data.x, plan.edges, plan.types)
+    reason = kg_validation_unsupported(model, z.shape[1], z.dtype, z.is_cuda, plan.rankings())
+    if reason is None and z.shape[1] != model.W.shape[1]:
+        reason = f'embedding width {z.shape[1]} against a DistMult table of width {model.W.shape[1]}'
+    if reason is not None:
+        return _fallback(trainer, reason)
+    out = plan.validate(trainer, model, data, pred_all, z)
     trainer.trainer_log['validation_path'] = 'prepared'
     return out
 

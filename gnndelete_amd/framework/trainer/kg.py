@@ -71,6 +71,12 @@ class KGTrainer(Trainer):
         model.eval()
         model = model.to(device)
         data = data.to(device)
+        if getattr(self.args, 'fused_validation', False):
+            # --fused_validation (gnndelete_amd/evalpass.py): the Dr typed graph and the decoded triples prepared once, one scoring launch
+            from ... import evalpass
+            out = evalpass.prepared_kg_validation(self, model, data, stage, pred_all, device)
+            if out is not None:
+                return out                  # (None: trainer_log['validation_path'] says why, and today's path runs)
         pos, neg = data[f'{stage}_pos_edge_index'], data[f'{stage}_neg_edge_index']
         etype = data[f'{stage}_edge_type']
         z = model(data.x, data.edge_index[:, data.dr_mask].contiguous(), data.edge_type[data.dr_mask].contiguous())

@@ -511,6 +511,57 @@ def graph_for(edge_index, num_nodes, mode):
     return CACHE.get(edge_index, num_nodes, mode)
 
 
+class _TypedRegistry:
+    """The typed counterpart of _GraphCache.pin: the per-graph index structures of a PINNED (edge_index, edge_type) pair - the
+    TypedNodeCSR ('nodes'), the relation-major CSR of the wide-width fallback ('rel') and RGATConv's edge orders ('orders') -
+    are built on first use and held until unpin, keyed on (num_nodes, num_relations, _version of both tensors).  ONE held
+    structure serves every conv that asks for it (nn.RGCNConv / nn.RGATConv look here before their own one-slot cache), so
+    conv1 and conv2 of a model share a graph, and the graphs of other pairs passing through the convs do not displace it.
+    An in-place edit of either tensor rebuilds (the stale structure is dropped).  A pair that is not pinned is not held:
+    get() returns None and the conv's one-slot cache decides as before.  (The prepared knowledge-graph validation,
+    gnndelete_amd/evalpass.py, pins its Dr message-passing edges.)"""
+
+    def __init__(self):
+        self.pins = {}                   # (id(edge_index), id(edge_type)) -> [edge_index, edge_type, pin count]
+        self.held = {}                   # the same key -> {(kind, num_nodes, num_relations): ((versions), structure)}
+
+    def _pin_of(self, edge_index, edge_type):
+        pin = self.pins.get((id(edge_index), id(edge_type)))
+        return pin if pin is not None and pin[0] is edge_index and pin[1] is edge_type else None
+
+    def pin(self, edge_index, edge_type):
+        self.pins.setdefault((id(edge_index), id(edge_type)), [edge_index, edge_type, 0])[2] += 1
+
+    def unpin(self, edge_index, edge_type):
+        pin = self._pin_of(edge_index, edge_type)
+        if pin is None:
+            return
+        pin[2] -= 1
+        if pin[2] <= 0:
+            del self.pins[(id(edge_index), id(edge_type))]
+            self.held.pop((id(edge_index), id(edge_type)), None)
+
+    def pinned(self, edge_index, edge_type):
+        return self._pin_of(edge_index, edge_type) is not None
+
+    def get(self, kind, edge_index, edge_type, num_nodes, num_relations, build):
+        """The held structure `kind` of a pinned pair (build() on first use or after an in-place edit); None for any other pair."""
+        if self._pin_of(edge_index, edge_type) is None:
+            return None
+        slot = self.held.setdefault((id(edge_index), id(edge_type)), {})
+        key, versions = (kind, int(num_nodes), int(num_relations)), (edge_index._version, edge_type._version)
+        entry = slot.get(key)
+        if entry is None or entry[0] != versions:
+            entry = slot[key] = (versions, build())
+        return entry[1]
+
+    def clear(self):
+        self.held.clear()
+
+
+TYPED = _TypedRegistry()
+
+
 def build_typed_csr(edge_index, edge_type, num_nodes, num_relations):
     """Relation-major CSR for R-GCN: virtual row r * n + i holds the in-edges of type r into i.
     Returns (rowptr[R*n+1], col, rowptr_t, col_t, inv_count_t) where the transposed arrays give,

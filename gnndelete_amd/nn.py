@@ -16,7 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .graph import TypedNodeCSR, build_typed_csr, graph_for
+from .graph import TYPED, TypedNodeCSR, build_typed_csr, graph_for
 
 
 def _glorot(*shape):
@@ -138,6 +138,10 @@ class RGCNConv(nn.Module):
         self._typed_nodes = None
 
     def _typed_csr(self, edge_index, edge_type, n):
+        held = TYPED.get('rel', edge_index, edge_type, n, self.num_relations,
+                         lambda: build_typed_csr(edge_index, edge_type, n, self.num_relations))
+        if held is not None:            # a pinned pair (graph.TYPED): one structure for every conv, outside the one-slot cache
+            return held
         c, key = self._typed, (_tensor_key(edge_index, edge_type), n)
         if c is None or c[0] != key:
             # the entry keeps the key tensors alive, so their storage cannot be recycled for another edge list
@@ -146,6 +150,10 @@ class RGCNConv(nn.Module):
         return c[1]
 
     def _typed_node_csr(self, edge_index, edge_type, n):
+        held = TYPED.get('nodes', edge_index, edge_type, n, self.num_relations,
+                         lambda: TypedNodeCSR(edge_index, edge_type, n, self.num_relations))
+        if held is not None:
+            return held
         c, key = self._typed_nodes, (_tensor_key(edge_index, edge_type), n)
         if c is None or c[0] != key:
             c = (key, TypedNodeCSR(edge_index, edge_type, n, self.num_relations), edge_index, edge_type)
@@ -219,6 +227,10 @@ class RGATConv(nn.Module):
         self._typed_nodes = None
 
     def _typed_node_csr(self, edge_index, edge_type, n):
+        held = TYPED.get('nodes', edge_index, edge_type, n, self.num_relations,
+                         lambda: TypedNodeCSR(edge_index, edge_type, n, self.num_relations))
+        if held is not None:
+            return held
         c, key = self._typed_nodes, (_tensor_key(edge_index, edge_type), n)
         if c is None or c[0] != key:
             c = (key, TypedNodeCSR(edge_index, edge_type, n, self.num_relations), edge_index, edge_type)
@@ -235,9 +247,19 @@ class RGATConv(nn.Module):
     def _edge_orders(self, edge_index, edge_type, n):
         """Index structure of one (edge_index, edge_type) pair, built once on the device and cached: the edges grouped by
         target (softmax segments), the relation-major typed CSR (rows r * n + i) and its transpose by source."""
+        held = TYPED.get('orders', edge_index, edge_type, n, self.num_relations,
+                         lambda: self._build_edge_orders(edge_index, edge_type, n))
+        if held is not None:
+            return held
         c, key = getattr(self, '_orders', None), (_tensor_key(edge_index, edge_type), n)
         if c is not None and c[0] == key:
             return c[1]
+        tc = self._build_edge_orders(edge_index, edge_type, n)
+        self._orders = (key, tc)
+        return tc
+
+    def _build_edge_orders(self, edge_index, edge_type, n):
+        """(depends on the pair, n and num_relations only: a pinned pair's orders are shared between convs)"""
         dev = edge_index.device
         src, dst, et = edge_index[0].long(), edge_index[1].long(), edge_type.long()
         r = self.num_relations
@@ -262,7 +284,6 @@ class RGATConv(nn.Module):
         inv_d = torch.empty_like(ord_d)
         inv_d[ord_d] = torch.arange(ord_d.numel(), device=dev)
         tc['inv_d'] = inv_d
-        self._orders = (key, tc)
         return tc
 
     def forward(self, x, edge_index, edge_type):

@@ -58,7 +58,9 @@ extern "C" {
                                 gd_rank_counts_f32, gd_subset_rank_metrics (+ its _workspace query): resampled AUC / AP without the
                                 batched sort (entries added: the version stays);
                                 gd_eval_edge_scores_f32, gd_row_nll_eval_f32 (+ their _workspace queries): the per-validation scoring of
-                                the prepared validation pass (entries added: the version stays) */
+                                the prepared validation pass (entries added: the version stays);
+                                gd_eval_triple_scores_f32 (+ its _workspace query): the same for the knowledge-graph trainers' DistMult
+                                triples (entries added: the version stays) */
 
 enum {
   GD_OK = 0,
@@ -1007,6 +1009,27 @@ int64_t gd_eval_edge_scores_workspace(int64_t m_all, int32_t d);
 int gd_eval_edge_scores_f32(const float* z, int64_t ld_z, int64_t n_nodes, int32_t d, const int64_t* src, const int64_t* dst,
                             int64_t n_pos, int64_t n_neg, int64_t n_df, int64_t n_dr, float* scores, double* stats,
                             int32_t* status, double* workspace, void* stream);
+
+/* The per-validation scoring of the prepared KNOWLEDGE-GRAPH validation (KGTrainer.eval under --fused_validation,
+ * framework/trainer/base.py:495-567 upstream).  ONE decoded triple list (src[k], etype[k], dst[k]), k < M, laid out as above
+ * [stage pos | stage neg | directed Df | Dr], DistMult table rel [n_rel, d] with row pitch ld_rel:
+ *     l_k = sum_j z[src[k], j] rel[etype[k], j] z[dst[k], j]    ((z_a rel) rounded, then one fma chain over z_b per lane: the
+ *                                                               association of gd_edge_dot_f32's DistMult decode)
+ *     scores[k] = l_k                   for the stage (k < n_pos + n_neg): upstream ranks and scores the stage WITHOUT sigmoid
+ *     scores[k] = sigmoid(l_k)          for Df / Dr, by gd_eval_edge_scores_f32's two branches (never NaN for finite inputs)
+ *     stats[0]  = (1 / (n_pos + n_neg)) sum over the stage of  max(l, 0) - l y + log1p(exp(-|l|)),   l = (double)scores[k],
+ *                 y = 1 for k < n_pos: binary_cross_entropy_with_logits, finite at any finite l; NaN without stage triples
+ *     stats[1], stats[2] = mean and POPULATION standard deviation of the Df scores, as gd_eval_edge_scores_f32
+ *     status[0] = 1 when an endpoint lies outside [0, n_nodes) or a type outside [0, n_rel), else 0: such a triple reads nothing
+ *                 and scores logit 0 (0 in the stage, 0.5 in Df / Dr); wrappers raise IndexError.
+ * The launch shape, the double partials, the finishing launch and the argument rules are gd_eval_edge_scores_f32's (the same
+ * bits on every call, no atomics); rel additionally 16-byte aligned with ld_rel % 4 == 0 and >= d, n_rel >= 1.
+ * workspace: gd_eval_triple_scores_workspace(M, d) doubles.  Two launches, graph-capturable. */
+int64_t gd_eval_triple_scores_workspace(int64_t m_all, int32_t d);
+int gd_eval_triple_scores_f32(const float* z, int64_t ld_z, int64_t n_nodes, int32_t d, const float* rel, int64_t ld_rel,
+                              int64_t n_rel, const int64_t* src, const int64_t* dst, const int64_t* etype, int64_t n_pos,
+                              int64_t n_neg, int64_t n_df, int64_t n_dr, float* scores, double* stats, int32_t* status,
+                              double* workspace, void* stream);
 
 /* The per-validation scoring of the prepared node-classification validation (NodeClassificationTrainer.eval under
  * --fused_validation, base.py:754-790 upstream) over the n_sel listed rows u = row_idx[i] (int32) of a pitched [n_rows, ld]
