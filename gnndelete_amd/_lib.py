@@ -42,6 +42,8 @@ PROTOTYPES = {
     'gd_rank_counts_f32': (ctypes.c_int, [_p, _i64, _p, _i64, _p, _p, _p]),
     'gd_subset_rank_workspace': (_i64, [_i64, _i64]),
     'gd_subset_rank_metrics': (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _p]),
+    'gd_subset_rank_metrics_drawn': (ctypes.c_int, [_p, _p, _p, _p, ctypes.c_uint64, ctypes.c_uint64, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _p]),
+    'gd_subset_draw': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, _i64, _i64, _i64, _p, _i64, _p]),
     'gd_rgcn_tile_kl': (ctypes.c_int32, [_i32, _i32, _i32, _i32]),
     'gd_rgcn_pack_weight_f32': (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     'gd_rgcn_wave_covers': (ctypes.c_int32, [_i32, _i32, _i32]),

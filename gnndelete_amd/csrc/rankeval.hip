@@ -23,6 +23,24 @@
 // atomics, a fixed thread-to-word mapping and a fixed reduction tree; no float atomics.  Every index read from memory
 // (idx, pos, run_end) is range-checked before it addresses anything: a NaN score or a broken index gives a meaningless
 // value, never an access outside the arrays.
+//
+// gd_subset_rank_metrics_drawn (--device_subsets) is the same kernel with another member source: phase 2 computes member j of
+// subset b instead of reading idx[b, j], so a ranking needs no index matrix and no launches that draw one.  The stream is a
+// keyed permutation of [0, m) per subset whose first k outputs are the subset - a pure function of (seed, draw, b, j, m) in
+// integer operations (fmix32 = the murmur3 32-bit finaliser, mix64 = the splitmix64 finaliser of common.h):
+//
+//   bits = max(6, bit_length(m - 1)) rounded up to even;  h = bits / 2;  mask = 2^h - 1            (32 <= m < 2^31: h <= 16)
+//   base = mix64(seed ^ mix64(draw));  kb = mix64(base + b);  key[r] = the low 32 bits of mix64(kb + r),  r = 0 .. 11
+//   P(v):  L = v >> h, R = v & mask;  twelve times (L, R) <- (R, L ^ (fmix32(R ^ key[r]) & mask));  (L << h) | R
+//   e(b, j) = the first of P(j), P(P(j)), ... below m                                              (cycle walking, uint32)
+//
+// P is a balanced Feistel network, a bijection of [0, 2^bits) whatever the round function; the walk from j < m stays on j's
+// cycle of P, which returns to j < m after at most 2^bits applications, so it ends and the loop's bound of 2^bits is never
+// reached; j -> e(b, j) is then a bijection of [0, m) (the permutation P induces on the subset [0, m) of its domain), so the
+// k members of a subset are distinct - the precondition above.  2^bits < 4 m: fewer than 4 applications per member on
+// average.  A subset's twelve keys are computed once per block (threads 0 .. 11, through LDS) and held in scalar registers.
+// The OR of phase 2 does not depend on order and phases 1, 3 and 4 are the same code, so the drawn entry gives the bits of
+// gd_subset_rank_metrics on the matrix gd_subset_draw writes.  gnndelete_amd/subsets.reference_draw restates the stream.
 #include "common.h"
 
 namespace gd {
@@ -56,6 +74,54 @@ __global__ __launch_bounds__(256) void rank_counts_kernel(const float* __restric
   leq[i] = lo;
 }
 
+constexpr int kDrawRounds = 12;                    // Feistel rounds of the subset stream: part of the stream, not a tuning knob
+
+inline int draw_half_bits(int64_t m) {             // h: half the width of the permutation's domain, 3 .. 16 for 32 <= m < 2^31
+  int bits = 6;
+  while (bits < 32 && (1ll << bits) < m) ++bits;   // bit_length(m - 1), at least 6
+  return (bits + 1) / 2;
+}
+
+__device__ __forceinline__ uint32_t fmix32(uint32_t x) {       // the murmur3 32-bit finaliser
+  x ^= x >> 16;
+  x *= 0x85ebca6bu;
+  x ^= x >> 13;
+  x *= 0xc2b2ae35u;
+  return x ^ (x >> 16);
+}
+
+// The keys of subset b into key[0 .. 11], the same in every lane (scalar registers).  Every thread of the block calls it
+// with the same (seed, draw, b); `slot` is the block's LDS row of kDrawRounds words.  Two barriers inside.
+__device__ __forceinline__ void draw_keys(uint64_t seed, uint64_t draw, uint64_t b, uint32_t* slot, uint32_t (&key)[kDrawRounds]) {
+  __syncthreads();                                              // (a block that loops over subsets: the last readers are done)
+  if (threadIdx.x < kDrawRounds) {
+    const uint64_t kb = mix64(mix64(seed ^ mix64(draw)) + b);
+    slot[threadIdx.x] = (uint32_t)mix64(kb + (uint64_t)threadIdx.x);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < kDrawRounds; ++r) key[r] = __builtin_amdgcn_readfirstlane(slot[r]);
+}
+
+// Member j (< m) of the subset with these keys: cycle walking on the Feistel permutation of [0, 2^(2h)).  In [0, m) always:
+// the bound of 2^(2h) applications is never reached (see above), and a value that reached it would be clamped.
+__device__ __forceinline__ uint32_t draw_member(uint32_t j, uint32_t m, int h, const uint32_t (&key)[kDrawRounds]) {
+  const uint32_t mask = (1u << h) - 1u;
+  uint32_t v = j;
+  for (uint64_t n = 0, bound = 1ull << (2 * h); n < bound; ++n) {
+    uint32_t l = v >> h, r = v & mask;
+#pragma unroll
+    for (int i = 0; i < kDrawRounds; ++i) {
+      const uint32_t f = l ^ (fmix32(r ^ key[i]) & mask);
+      l = r;
+      r = f;
+    }
+    v = (l << h) | r;
+    if (v < m) return v;
+  }
+  return j;                                                     // (unreachable for j < m)
+}
+
 // a word this launch stored or OR-ed: served by L2, never by a line the L1 may have kept
 __device__ __forceinline__ uint32_t load_l2(uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // end of a phase: this wave's stores and atomics have reached L2, then the block meets
@@ -64,12 +130,16 @@ __device__ __forceinline__ void phase_end() {
   __syncthreads();
 }
 
+// kDrawn = false: member j of subset b is idx[b * ld_idx + j] (seed / draw unused); true: draw_member (idx / ld_idx unused)
+template <bool kDrawn>
 __global__ __launch_bounds__(kRankBlock) void subset_rank_kernel(const int32_t* __restrict__ u2, const int32_t* __restrict__ ge_at,
                                                                  const int32_t* __restrict__ run_end, const int32_t* __restrict__ pos,
-                                                                 const int64_t* __restrict__ idx, int64_t ld_idx, int64_t n_sub, int32_t k,
-                                                                 int32_t m, int32_t n_ref, double* __restrict__ auc,
-                                                                 double* __restrict__ ap, uint32_t* workspace, int64_t row_words) {
+                                                                 const int64_t* __restrict__ idx, int64_t ld_idx, uint64_t seed,
+                                                                 uint64_t draw, int half_bits, int64_t n_sub, int32_t k, int32_t m,
+                                                                 int32_t n_ref, double* __restrict__ auc, double* __restrict__ ap,
+                                                                 uint32_t* workspace, int64_t row_words) {
   __shared__ int32_t wave_count[2][kRankWaves];
+  __shared__ uint32_t draw_slot[kDrawRounds];
   __shared__ long long wave_u2[kRankWaves];
   __shared__ double wave_ap[kRankWaves];
   const int64_t b = blockIdx.x;
@@ -84,13 +154,25 @@ __global__ __launch_bounds__(kRankBlock) void subset_rank_kernel(const int32_t* 
   phase_end();
 
   // 2: the members' bits, by sorted position
-  const int64_t* row = idx + b * ld_idx;
-  for (int64_t j = t; j < k; j += kRankBlock) {
-    const int64_t e = row[j];
-    if (e < 0 || e >= m) continue;
-    const int32_t p = pos[e];
-    if (p < 0 || p >= m) continue;
-    __hip_atomic_fetch_or(bits + (p >> 5), 1u << (p & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if constexpr (kDrawn) {
+    uint32_t key[kDrawRounds];
+    draw_keys(seed, draw, (uint64_t)b, draw_slot, key);
+    for (int64_t j = t; j < k; j += kRankBlock) {
+      const int64_t e = draw_member((uint32_t)j, (uint32_t)m, half_bits, key);
+      if (e < 0 || e >= m) continue;
+      const int32_t p = pos[e];
+      if (p < 0 || p >= m) continue;
+      __hip_atomic_fetch_or(bits + (p >> 5), 1u << (p & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  } else {
+    const int64_t* row = idx + b * ld_idx;
+    for (int64_t j = t; j < k; j += kRankBlock) {
+      const int64_t e = row[j];
+      if (e < 0 || e >= m) continue;
+      const int32_t p = pos[e];
+      if (p < 0 || p >= m) continue;
+      __hip_atomic_fetch_or(bits + (p >> 5), 1u << (p & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
   phase_end();
 
@@ -159,6 +241,18 @@ __global__ __launch_bounds__(kRankBlock) void subset_rank_kernel(const int32_t* 
   }
 }
 
+// gd_subset_draw: block (x, y) writes members x * 1024 .. of the subsets y, y + gridDim.y, ...; one thread per member
+__global__ __launch_bounds__(kRankBlock) void subset_draw_kernel(uint64_t seed, uint64_t draw, int half_bits, int64_t n_sub, int32_t k,
+                                                                 int32_t m, int64_t* __restrict__ out, int64_t ld_out) {
+  __shared__ uint32_t draw_slot[kDrawRounds];
+  const int64_t j = (int64_t)blockIdx.x * kRankBlock + threadIdx.x;
+  for (int64_t b = blockIdx.y; b < n_sub; b += gridDim.y) {      // (uniform over the block: draw_keys holds barriers)
+    uint32_t key[kDrawRounds];
+    draw_keys(seed, draw, (uint64_t)b, draw_slot, key);
+    if (j < k) out[b * ld_out + j] = (int64_t)draw_member((uint32_t)j, (uint32_t)m, half_bits, key);
+  }
+}
+
 }  // namespace gd
 
 extern "C" int gd_rank_counts_f32(const float* ref, int64_t n_ref, const float* query, int64_t m, int32_t* less, int32_t* leq,
@@ -192,7 +286,43 @@ extern "C" int gd_subset_rank_metrics(const int32_t* u2, const int32_t* ge_at, c
   GD_REQUIRE(workspace_bytes >= gd_subset_rank_workspace(n_sub, m), GD_E_WORKSPACE,
              "gd_subset_rank_metrics: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
              (long long)gd_subset_rank_workspace(n_sub, m));
-  hipLaunchKernelGGL(subset_rank_kernel, dim3((unsigned)n_sub), dim3(kRankBlock), 0, (hipStream_t)stream, u2, ge_at, run_end, pos, idx, ld_idx,
-                     n_sub, (int32_t)k, (int32_t)m, (int32_t)n_ref, auc, ap, (uint32_t*)workspace, rank_row_words(m));
+  hipLaunchKernelGGL(subset_rank_kernel<false>, dim3((unsigned)n_sub), dim3(kRankBlock), 0, (hipStream_t)stream, u2, ge_at, run_end, pos, idx,
+                     ld_idx, (uint64_t)0, (uint64_t)0, 0, n_sub, (int32_t)k, (int32_t)m, (int32_t)n_ref, auc, ap, (uint32_t*)workspace,
+                     rank_row_words(m));
   return launched("subset_rank_metrics");
+}
+
+extern "C" int gd_subset_rank_metrics_drawn(const int32_t* u2, const int32_t* ge_at, const int32_t* run_end, const int32_t* pos,
+                                            uint64_t seed, uint64_t draw, int64_t n_sub, int64_t k, int64_t m, int64_t n_ref, double* auc,
+                                            double* ap, void* workspace, int64_t workspace_bytes, void* stream) {
+  using namespace gd;
+  GD_REQUIRE(n_sub >= 0 && n_sub < (1ll << 31) && m >= 1 && m < (1ll << 31) && k >= 1 && k <= m && n_ref >= 1 && n_ref < (1ll << 30),
+             GD_E_DIM, "gd_subset_rank_metrics_drawn: n_sub=%lld k=%lld m=%lld n_ref=%lld out of range (1 <= k <= m < 2^31, 1 <= n_ref < 2^30)",
+             (long long)n_sub, (long long)k, (long long)m, (long long)n_ref);
+  GD_REQUIRE(m >= 32, GD_E_DIM, "gd_subset_rank_metrics_drawn: a pool of m=%lld (the subset stream takes 32 and more)", (long long)m);
+  if (n_sub == 0) return GD_OK;
+  GD_REQUIRE(u2 && ge_at && run_end && pos && auc && ap && workspace, GD_E_NULL, "gd_subset_rank_metrics_drawn: null pointer");
+  GD_REQUIRE(aligned16(workspace), GD_E_ALIGN, "gd_subset_rank_metrics_drawn: workspace not 16-byte aligned");
+  GD_REQUIRE(workspace_bytes >= gd_subset_rank_workspace(n_sub, m), GD_E_WORKSPACE,
+             "gd_subset_rank_metrics_drawn: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+             (long long)gd_subset_rank_workspace(n_sub, m));
+  hipLaunchKernelGGL(subset_rank_kernel<true>, dim3((unsigned)n_sub), dim3(kRankBlock), 0, (hipStream_t)stream, u2, ge_at, run_end, pos,
+                     (const int64_t*)nullptr, (int64_t)0, seed, draw, draw_half_bits(m), n_sub, (int32_t)k, (int32_t)m, (int32_t)n_ref, auc, ap,
+                     (uint32_t*)workspace, rank_row_words(m));
+  return launched("subset_rank_metrics_drawn");
+}
+
+extern "C" int gd_subset_draw(uint64_t seed, uint64_t draw, int64_t n_sub, int64_t k, int64_t m, int64_t* out, int64_t ld_out,
+                              void* stream) {
+  using namespace gd;
+  GD_REQUIRE(n_sub >= 0 && n_sub < (1ll << 31) && m >= 32 && m < (1ll << 31) && k >= 1 && k <= m, GD_E_DIM,
+             "gd_subset_draw: n_sub=%lld k=%lld m=%lld out of range (1 <= k <= m, 32 <= m < 2^31)", (long long)n_sub, (long long)k,
+             (long long)m);
+  if (n_sub == 0) return GD_OK;
+  GD_REQUIRE(out, GD_E_NULL, "gd_subset_draw: null pointer");
+  GD_REQUIRE(ld_out >= k, GD_E_DIM, "gd_subset_draw: ld_out=%lld below k=%lld", (long long)ld_out, (long long)k);
+  const unsigned rows = (unsigned)(n_sub < 65535 ? n_sub : 65535);
+  hipLaunchKernelGGL(subset_draw_kernel, dim3((unsigned)((k + kRankBlock - 1) / kRankBlock), rows), dim3(kRankBlock), 0, (hipStream_t)stream,
+                     seed, draw, draw_half_bits(m), n_sub, (int32_t)k, (int32_t)m, out, ld_out);
+  return launched("subset_draw");
 }

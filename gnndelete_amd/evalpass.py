@@ -28,11 +28,16 @@ KGTrainer.eval (R-GCN / R-GAT, DistMult) validates the same way on a KGValidatio
 in graph.TYPED (ONE typed graph for conv1 and conv2 instead of one each per validation), gd_eval_triple_scores_f32 over one
 decoded triple list (raw logits and BCE-with-logits for the stage, as upstream scores it; sigmoid for Df / Dr), the rank kernels
 for both rankings.  Its staleness check also compares contents, because the knowledge-graph loops move the data to the host
-between validations; its 500 Dr subsets stay upstream's fresh draws per call.  reference_triple_scores is that entry's oracle."""
+between validations; its 500 Dr subsets stay upstream's fresh draws per call.  reference_triple_scores is that entry's oracle.
+
+--device_subsets (gnndelete_amd/subsets.py) takes the 500 subsets out of both plans: one host randint gives a seed, and
+rankeval.subset_auc_ap_drawn computes every subset's members inside the rank kernel - no permutations, no [500, |Df|] index
+matrix.  The subsets come from a stream of the project's own, not from upstream's generator calls: df_auc / df_aup are the same
+statistic over other subsets.  trainer_log['subset_draw'] says 'device' or 'upstream: <reason>'."""
 import numpy as np
 import torch
 
-from . import rankeval
+from . import rankeval, subsets
 
 MAX_WIDTH = 256          # embedding width of gd_eval_edge_scores_f32 / classes of gd_row_nll_eval_f32
 
@@ -289,6 +294,8 @@ def _stamp(*tensors):
 class LinkValidationPlan:
     """Everything of a link-prediction validation that depends only on the request; one per (Trainer, stage)."""
 
+    N_SUBSETS = 500
+
     @staticmethod
     def sources(data, stage, original):
         """The tensors the plan is derived from, in the order of its staleness key."""
@@ -319,8 +326,10 @@ class LinkValidationPlan:
         self.decoded, self.src, self.dst = decoded, decoded[0], decoded[1]
         n_pos, n_neg, n_df, n_dr = self.segments
         self.all_positives = torch.arange(n_pos, device=decoded.device)[None]
-        self.subset_index = None
-        if n_df > 0:
+        self.subset_index = self.subset_seed = None
+        # --device_subsets: no index matrix and none of Trainer._ensure_df_subsets's draws; validate() draws ONE seed
+        self.drawn = bool(getattr(trainer.args, 'device_subsets', False)) and n_df > 0 and subsets.device_subsets_unsupported(n_dr, n_df) is None
+        if n_df > 0 and not self.drawn:
             # exactly Trainer.eval's calls: the same draws from the host generator in the same order
             trainer._ensure_df_subsets(n_dr, n_df, decoded.device)
             if getattr(trainer, '_df_subset_index', None) is None or trainer._df_subset_index.device != decoded.device:
@@ -330,7 +339,7 @@ class LinkValidationPlan:
 
     def rankings(self):
         n_pos, n_neg, n_df, n_dr = self.segments
-        return [(n_neg, n_pos, n_pos)] + ([(n_df, n_dr, self.subset_index.shape[1])] if n_df > 0 else [])
+        return [(n_neg, n_pos, n_pos)] + ([(n_df, n_dr, n_df if self.drawn else self.subset_index.shape[1])] if n_df > 0 else [])
 
     def release(self):
         if getattr(self, '_pinned', False):
@@ -358,7 +367,14 @@ class LinkValidationPlan:
         parts = [stats, status.double(), auc, aup]
         if n_df > 0:
             df_score = scores[n_stage:n_stage + n_df]
-            auc, aup = rankeval.subset_auc_ap(df_score, scores[n_stage + n_df:], self.subset_index)
+            if self.drawn:
+                if self.subset_seed is None:
+                    # the plan's ONE host call, the one the large-pool branch of Trainer._ensure_df_subsets makes; the seed is
+                    # the plan's, so every validation of the request ranks the same 500 subsets, as today
+                    self.subset_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)))
+                auc, aup = rankeval.subset_auc_ap_drawn(df_score, scores[n_stage + n_df:], self.subset_seed, 0, self.N_SUBSETS, n_df)
+            else:
+                auc, aup = rankeval.subset_auc_ap(df_score, scores[n_stage + n_df:], self.subset_index)
             parts += [auc.mean()[None], aup.mean()[None]]
         host = torch.cat(parts).tolist()                             # the validation's ONE read of its scalars
         if host[3] != 0.0:
@@ -429,7 +445,9 @@ class KGValidationPlan:
     the new tensors as the plan's sources and keep everything derived; anything else rebuilds.
 
     The 500 Dr subsets are NOT the plan's: upstream draws them fresh on every call, and validate() makes the same generator
-    calls in the same order as KGTrainer.eval, so a seed gives the same subsets and leaves the same host random stream."""
+    calls in the same order as KGTrainer.eval, so a seed gives the same subsets and leaves the same host random stream.  Under
+    --device_subsets (validate(drawn=True)) a validation makes ONE of those calls, the large-pool branch's randint, and the
+    rank kernel draws the subsets from its value (subsets.py): subset_seed holds it, subsets stays None."""
 
     N_SUBSETS = 500
 
@@ -467,7 +485,7 @@ class KGValidationPlan:
         self.decoded, self.src, self.dst = decoded, decoded[0], decoded[1]
         self.etype = torch.cat(types, dim=0).long().contiguous()
         self.all_positives = torch.arange(self.segments[0], device=decoded.device)[None]
-        self.z = self.scores = self.subsets = None                   # of the latest validation
+        self.z = self.scores = self.subsets = self.subset_seed = None   # of the latest validation
 
     def current(self, data, stage, original, device):
         """Is the plan still that of (data, stage)?  True on an identity hit, or after adopting tensors of equal contents."""
@@ -514,8 +532,9 @@ class KGValidationPlan:
         return picks
 
     @torch.no_grad()
-    def validate(self, trainer, model, data, pred_all=False, z=None):
-        """One validation -> KGTrainer.eval's tuple.  z: model(data.x, self.edges, self.types) when the caller has run it."""
+    def validate(self, trainer, model, data, pred_all=False, z=None, drawn=False):
+        """One validation -> KGTrainer.eval's tuple.  z: model(data.x, self.edges, self.types) when the caller has run it;
+        drawn: --device_subsets applies (the 500 subsets come from subsets.py's stream inside the rank kernel)."""
         from .framework.trainer.base import _all_pairs
         stage = self.stage
         n_pos, n_neg, n_df, n_dr = self.segments
@@ -528,8 +547,14 @@ class KGValidationPlan:
         parts = [stats, status.double(), auc, aup]
         if n_df > 0:
             df_score = scores[n_stage:n_stage + n_df]
-            self.subsets = self._draw_subsets(trainer, n_dr, n_df, scores.device)
-            auc, aup = rankeval.subset_auc_ap(df_score, scores[n_stage + n_df:], self.subsets)
+            if drawn:
+                # ONE host call, the one the large-pool branch of _draw_subsets makes: above FAST_SUBSETS_ABOVE the host random
+                # stream after a validation is the one without the flag
+                self.subsets, self.subset_seed = None, int(torch.randint(0, 2 ** 31 - 1, (1,)))
+                auc, aup = rankeval.subset_auc_ap_drawn(df_score, scores[n_stage + n_df:], self.subset_seed, 0, self.N_SUBSETS, n_df)
+            else:
+                self.subsets = self._draw_subsets(trainer, n_dr, n_df, scores.device)
+                auc, aup = rankeval.subset_auc_ap(df_score, scores[n_stage + n_df:], self.subsets)
             parts += [auc.mean()[None], aup.mean()[None]]
         host = torch.cat(parts).tolist()                             # the validation's ONE read of its scalars
         if host[3] != 0.0:
@@ -547,11 +572,24 @@ class KGValidationPlan:
 
 
 # ---------------------------------------------------------------------------------------------- the trainers' entry
+def subset_draw(trainer, reason):
+    """Under --device_subsets: trainer_log['subset_draw'] = 'device' (reason None) or 'upstream: <reason>', a reason printed once;
+    returns whether the device draws.  Without the flag: False, nothing recorded."""
+    if not getattr(trainer.args, 'device_subsets', False):
+        return False
+    how = 'device' if reason is None else f'upstream: {reason}'
+    if reason is not None and trainer.trainer_log.get('subset_draw') != how:
+        print(f'--device_subsets: {reason}; drawing the validation subsets as upstream does', flush=True)
+    trainer.trainer_log['subset_draw'] = how
+    return reason is None
+
+
 def _fallback(trainer, reason):
     path = f'torch: {reason}'
     if trainer.trainer_log.get('validation_path') != path:
         print(f'--fused_validation: {reason}; validating on the torch path', flush=True)
     trainer.trainer_log['validation_path'] = path
+    subset_draw(trainer, f'the prepared pass fell back ({reason})')
     return None
 
 
@@ -579,6 +617,8 @@ def prepared_link_validation(trainer, model, data, stage, pred_all, device):
     reason = validation_unsupported(model, 'linkpred', z.shape[1], z.dtype, z.is_cuda, plan.rankings())
     if reason is not None:
         return _fallback(trainer, reason)
+    if plan.segments[2] > 0:
+        subset_draw(trainer, None if plan.drawn else subsets.device_subsets_unsupported(plan.segments[3], plan.segments[2]))
     out = plan.validate(model, data, pred_all, z)
     trainer.trainer_log['validation_path'] = 'prepared'
     return out
@@ -607,7 +647,9 @@ def prepared_kg_validation(trainer, model, data, stage, pred_all, device):
         reason = f'embedding width {z.shape[1]} against a DistMult table of width {model.W.shape[1]}'
     if reason is not None:
         return _fallback(trainer, reason)
-    out = plan.validate(trainer, model, data, pred_all, z)
+    n_df, n_dr = plan.segments[2:]
+    drawn = n_df > 0 and subset_draw(trainer, subsets.device_subsets_unsupported(n_dr, n_df))
+    out = plan.validate(trainer, model, data, pred_all, z, drawn)
     trainer.trainer_log['validation_path'] = 'prepared'
     return out
 

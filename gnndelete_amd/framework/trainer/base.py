@@ -285,6 +285,9 @@ class Trainer:
             out = evalpass.prepared_link_validation(self, model, data, stage, pred_all, device)
             if out is not None:
                 return out                  # (None: trainer_log['validation_path'] says why, and today's path runs)
+        elif getattr(self.args, 'device_subsets', False):
+            from ... import evalpass
+            evalpass.subset_draw(self, '--fused_validation is missing')
         pos_edge_index = data[f'{stage}_pos_edge_index']
         neg_edge_index = data[f'{stage}_neg_edge_index']
         z = model(data.x, self._message_passing_edges(data))

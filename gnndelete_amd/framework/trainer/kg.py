@@ -77,6 +77,9 @@ class KGTrainer(Trainer):
             out = evalpass.prepared_kg_validation(self, model, data, stage, pred_all, device)
             if out is not None:
                 return out                  # (None: trainer_log['validation_path'] says why, and today's path runs)
+        elif getattr(self.args, 'device_subsets', False):
+            from ... import evalpass
+            evalpass.subset_draw(self, '--fused_validation is missing')
         pos, neg = data[f'{stage}_pos_edge_index'], data[f'{stage}_neg_edge_index']
         etype = data[f'{stage}_edge_type']
         z = model(data.x, data.edge_index[:, data.dr_mask].contiguous(), data.edge_type[data.dr_mask].contiguous())

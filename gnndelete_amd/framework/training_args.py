@@ -72,6 +72,7 @@ EXTRA_FLAGS = [
     ('device_negatives', None, False, 'where --fused_backbone / --fused_edgeprob applies: draw each epoch\'s negatives on the device (seeded by --random_seed; a different random stream than the host sampler) and merge them into the decoder\'s incidence list there, no host work between epochs'),
     ('fused_eval', None, False, 'link-prediction validation / test (Trainer.eval): rank the 500 resampled Df-vs-Dr AUC / AUP and the stage\'s AUC / AUP on the HIP rank kernels (one sort of the Dr scores per validation, a bitmap pass per subset) instead of the batched [500, 2|Df|] sort; AUC bit-equal, AUP within 1e-12'),
     ('fused_validation', None, False, 'validation / test of the link-prediction, node-classification and knowledge-graph trainers (Trainer.eval, NodeClassificationTrainer.eval, KGTrainer.eval): build what depends only on the request once - the message-passing graph (for R-GCN / R-GAT one typed graph shared by both convs, kept across the mini-batch loops\' host round trip), one decoded edge or triple list, the 500 Dr subsets (knowledge graphs: drawn fresh per validation, as upstream), the val_mask rows - and score each validation with one HIP launch pair (sigmoid scores, loss, Df mean / std; or NLL and accuracy) and one host read; decides over --fused_eval where it applies; scores come from the kernel\'s own sigmoid, so values are not bit-equal to the default path'),
+    ('device_subsets', None, False, 'where --fused_validation runs the prepared pass (Trainer.eval, KGTrainer.eval): draw the 500 Dr subsets of the Df ranking inside the rank kernel from one host randint (gnndelete_amd/subsets.py: a keyed permutation per subset, no generator state) instead of 500 permutations and a [500, |Df|] index matrix; reproducible per seed, but a different random stream than upstream\'s draws: df_auc / df_aup (validation and test) are the same statistic over other subsets; pools under 32 edges keep upstream\'s draw'),
     ('fused_row_losses', None, False, 'with --loss_fct kld_mean / kld_sum / cosine_mean / cosine_sum: run the full-batch node-embedding step on the fused HIP engine (folded row losses) instead of the autograd loop'),
     ('no_fused_step', None, False, 'use the autograd path even where the fused hipGraph step applies'),
     ('no_layer1_cache', None, False, 'recompute the frozen layer-1 output every epoch as upstream does (identical results)'),

@@ -20,7 +20,10 @@ The AUC's numerator is an exact integer, so it is the same double as metrics.bat
 sum over distinct thresholds with the recall step of a run of equal scores spread over the run's members, equal to
 metrics.batched_average_precision within rounding (a few 1e-16).  The scores are ranked as given: hand in the same fp32
 sigmoid outputs the torch path ranks, so that saturated scores tie the same way.  reference_subset_auc_ap restates the
-formulas in numpy and is the kernels' CPU oracle next to framework/metrics.py."""
+formulas in numpy and is the kernels' CPU oracle next to framework/metrics.py.
+
+subset_auc_ap_drawn (--device_subsets) is the same ranking without an index matrix: gd_subset_rank_metrics_drawn computes the
+members of every subset from (seed, draw) where the other entry reads idx (gnndelete_amd/subsets.py: the stream)."""
 import numpy as np
 import torch
 
@@ -115,7 +118,6 @@ def subset_auc_ap(ref, pool, idx):
     ref [n_ref], pool [m]: float32 device tensors; idx [B, k] (or [k]): int64 pool indices on the same device, any row stride.
     PRECONDITION: the indices of a row are DISTINCT (the trainer's rows are randperm(m)[:k]); a repeated index counts once in
     the ranking but k times in the divisor.  Raises ValueError where fused_eval_unsupported gives a reason."""
-    from . import _lib
     from ._lib import check, ptr, stream_ptr
     if idx.dim() == 1:
         idx = idx[None]
@@ -128,7 +130,19 @@ def subset_auc_ap(ref, pool, idx):
         raise ValueError(f'subset_auc_ap: {reason}')
     if k > 1 and idx.stride(1) != 1:
         idx = idx.contiguous()
-    dev = pool.device
+    L, dev, (u2, ge_at, run_end, pos), (ws, auc, ap) = _prepare(ref, pool, n_sub, 'subset_auc_ap')
+    with torch.cuda.device(dev):
+        check(L.gd_subset_rank_metrics(ptr(u2), ptr(ge_at), ptr(run_end), ptr(pos), ptr(idx), idx.stride(0) if n_sub > 1 else k, n_sub,
+                                       k, m, n_ref, ptr(auc), ptr(ap), ptr(ws), 4 * ws.numel(), stream_ptr(dev)),
+              'gd_subset_rank_metrics')
+    return auc, ap
+
+
+def _prepare(ref, pool, n_sub, who):
+    """What a ranking of n_sub subsets needs before its per-subset pass -> (library, device, (u2, ge_at, run_end, pos) by the
+    formulas above, (workspace, auc, ap) to be filled)."""
+    from . import _lib
+    n_ref, m, dev = ref.numel(), pool.numel(), pool.device
     # once per call, O(m log m): the pool in descending order and where each of its scores falls among the negatives
     ref_sorted = torch.sort(ref.reshape(-1)).values
     sorted_pool, order = torch.sort(pool.reshape(-1), descending=True)
@@ -145,12 +159,30 @@ def subset_auc_ap(ref, pool, idx):
     L = _lib.lib()
     n_bytes = L.gd_subset_rank_workspace(n_sub, m)
     if n_bytes < 0:
-        raise ValueError(f'subset_auc_ap: {n_sub} subsets of a pool of {m} are out of range')
+        raise ValueError(f'{who}: {n_sub} subsets of a pool of {m} are out of range')
     ws = torch.empty(n_bytes // 4 + 4, dtype=torch.int32, device=dev)
     auc = torch.empty(n_sub, dtype=torch.float64, device=dev)
     ap = torch.empty(n_sub, dtype=torch.float64, device=dev)
+    return L, dev, (u2, ge_at, run_end, pos), (ws, auc, ap)
+
+
+def subset_auc_ap_drawn(ref, pool, seed, draw, n_sub, k):
+    """subset_auc_ap(ref, pool, subsets.draw(seed, draw, n_sub, k, pool.numel())), bit for bit, without the index matrix:
+    gd_subset_rank_metrics_drawn computes member j of subset b (subsets.py: the stream) where the other entry reads idx[b, j].
+    ref [n_ref], pool [m]: float32 device tensors, m >= 32.  Raises ValueError where fused_eval_unsupported or
+    subsets.device_subsets_unsupported gives a reason."""
+    from ._lib import check, ptr, stream_ptr
+    from .subsets import device_subsets_unsupported
+    on_gpu = ref.is_cuda and pool.is_cuda and ref.device == pool.device
+    n_ref, m, n_sub, k = ref.numel(), pool.numel(), int(n_sub), int(k)
+    reason = fused_eval_unsupported(n_ref, m, k, on_gpu, ref.dtype if ref.dtype == pool.dtype else pool.dtype)
+    if reason is None:
+        reason = device_subsets_unsupported(m, k)
+    if reason is not None:
+        raise ValueError(f'subset_auc_ap_drawn: {reason}')
+    L, dev, (u2, ge_at, run_end, pos), (ws, auc, ap) = _prepare(ref, pool, n_sub, 'subset_auc_ap_drawn')
     with torch.cuda.device(dev):
-        check(L.gd_subset_rank_metrics(ptr(u2), ptr(ge_at), ptr(run_end), ptr(pos), ptr(idx), idx.stride(0) if n_sub > 1 else k, n_sub,
-                                       k, m, n_ref, ptr(auc), ptr(ap), ptr(ws), 4 * ws.numel(), stream_ptr(dev)),
-              'gd_subset_rank_metrics')
+        check(L.gd_subset_rank_metrics_drawn(ptr(u2), ptr(ge_at), ptr(run_end), ptr(pos), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                             int(draw) & 0xFFFFFFFFFFFFFFFF, n_sub, k, m, n_ref, ptr(auc), ptr(ap), ptr(ws), 4 * ws.numel(),
+                                             stream_ptr(dev)), 'gd_subset_rank_metrics_drawn')
     return auc, ap

@@ -60,7 +60,9 @@ extern "C" {
                                 gd_eval_edge_scores_f32, gd_row_nll_eval_f32 (+ their _workspace queries): the per-validation scoring of
                                 the prepared validation pass (entries added: the version stays);
                                 gd_eval_triple_scores_f32 (+ its _workspace query): the same for the knowledge-graph trainers' DistMult
-                                triples (entries added: the version stays) */
+                                triples (entries added: the version stays);
+                                gd_subset_rank_metrics_drawn, gd_subset_draw: the 500 validation subsets drawn inside the rank kernel
+                                (entries added: the version stays) */
 
 enum {
   GD_OK = 0,
@@ -417,6 +419,34 @@ int64_t gd_subset_rank_workspace(int64_t n_sub, int64_t m);
 int gd_subset_rank_metrics(const int32_t* u2, const int32_t* ge_at, const int32_t* run_end, const int32_t* pos, const int64_t* idx,
                            int64_t ld_idx, int64_t n_sub, int64_t k, int64_t m, int64_t n_ref, double* auc, double* ap,
                            void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The validation subsets drawn on the device (--device_subsets; csrc/rankeval.hip; gnndelete_amd/subsets.py holds the wrapper and
+ * the numpy restatement).  They stand in for the draws of the reference's trainers - base.py:530-539, the knowledge-graph
+ * trainer's 500 fresh torch.randperm(|Dr|)[:|Df|] per evaluation, and base.py:263-268, the link trainer's 500 drawn once per
+ * request - with a counter-based stream of their own: subset b of draw `draw` under `seed` is the first k outputs of a keyed
+ * permutation of [0, m), a pure function of (seed, draw, b, j, m) in integer operations, no generator state.  It is NOT the
+ * reference's random stream.  With mix64 the splitmix64 finaliser and fmix32 the murmur3 32-bit finaliser
+ * (h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16):
+ *     bits = max(6, bit_length(m - 1)) rounded up to even;  h = bits / 2;  mask = 2^h - 1
+ *     base = mix64(seed ^ mix64(draw));  kb = mix64(base + b);  key[r] = the low 32 bits of mix64(kb + r),  r = 0 .. 11
+ *     P(v):  L = v >> h, R = v & mask;  twelve times (L, R) <- (R, L ^ (fmix32(R ^ key[r]) & mask));  (L << h) | R
+ *     e(b, j) = the first of P(j), P(P(j)), ... that is below m                       (cycle walking; uint32 throughout)
+ * P is a bijection of [0, 2^bits) and the walk from j < m returns to j at the latest, so it ends (the loop is bounded by
+ * 2^bits applications, never reached) and j -> e(b, j) is a bijection of [0, m): the k members of a subset are distinct.
+ * 2^bits < 4 m: fewer than 4 applications per member on average.  32 <= m < 2^31 (below 32 the domain is too narrow for the
+ * twelve rounds to mix: GD_E_DIM).
+ *
+ * gd_subset_rank_metrics_drawn: gd_subset_rank_metrics with (seed, draw) in place of (idx, ld_idx) - the same kernel, its
+ * second phase computing member j of subset b instead of reading idx[b, j]; auc / ap are the bits gd_subset_rank_metrics
+ * gives on the matrix gd_subset_draw writes.  Refuses m < 32; every other refusal, the workspace (gd_subset_rank_workspace)
+ * and the guarantees are gd_subset_rank_metrics's own.  One launch; no index matrix is read or written.
+ *
+ * gd_subset_draw: out[b * ld_out + j] = e(b, j) for b < n_sub, j < k as int64; ld_out >= k, entries behind k are not written.
+ * 0 <= n_sub < 2^31, 1 <= k <= m (GD_E_DIM otherwise); n_sub == 0: GD_OK, no launch.  One launch, one thread per member. */
+int gd_subset_rank_metrics_drawn(const int32_t* u2, const int32_t* ge_at, const int32_t* run_end, const int32_t* pos, uint64_t seed,
+                                 uint64_t draw, int64_t n_sub, int64_t k, int64_t m, int64_t n_ref, double* auc, double* ap,
+                                 void* workspace, int64_t workspace_bytes, void* stream);
+int gd_subset_draw(uint64_t seed, uint64_t draw, int64_t n_sub, int64_t k, int64_t m, int64_t* out, int64_t ld_out, void* stream);
 
 /* The non-MSE row losses of the reference's loss zoo (framework/trainer/gnndelete_nodeemb.py:18-28), value per row
  * pair and gradient with respect to a, in one pass; rows of a / b optionally gathered through ia / ib (int64, NULL =
