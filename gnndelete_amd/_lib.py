@@ -69,6 +69,9 @@ PROTOTYPES = {
     'gd_rows_gemm_ws_covers': (ctypes.c_int, [_i32, _i32, _i32]),
     'gd_rows_gemm_accumulate_f32': (ctypes.c_int, [_p, _i64, _p, _i32, _p, _i32, _i32, _i32, _p, _i64, _p]),
     'gd_rows_gemm_select_f32': (ctypes.c_int, [_p, _p, _p, _i64, _p, _i32, _p, _i32, _i32, _i32, _p, _i32, _p, _i64, _p]),
+    'gd_rows_gemm_select_chain_covers': (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32]),
+    'gd_rows_gemm_select_chain_f32': (ctypes.c_int, [_p, _i64, _p, _i32, _p, _p, _p, _i64, _p, _i64, _p, _i32, _p, _i32, _i32, _i32,
+                                                     _p, _i64, _p]),
     'gd_rows_gemm_dots_f32': (ctypes.c_int, [_p, _p, _p, _i64, _p, _i32, _i32, _i32, _p, _i32, _p, _i64, _p, _i32, _p, _p, _p, _p,
                                              _p]),
     'gd_rows_gemm_signs_f32': (ctypes.c_int, [_p, _i64, _p, _i32, _p, _i32, _i32, _i32, _p, _i32, _p, _i64, _p, _p, _p]),

@@ -444,7 +444,238 @@ int rows_gemm_ws_try(const float* in, int64_t ld_in, const int32_t* idx, int32_t
 #undef GD_WS_SHAPE
 }
 
+// ---- The chained select product (gd_rows_gemm_select_chain_f32): conv2's Linear over a layer-1 output that lives in two places -
+// z on the LISTED rows (the Del-1 rows) and nowhere yet on the EXPLICIT rows, where only a = A^ x exists:
+//     listed row    out[row] = relu(z[row]) W2                                  (the <128, 64, 0, HASIDX, RELU> loop above, bit for bit)
+//     explicit row  h = a[row] W1 + b1 -> pre[row];  out[row] = relu(h) W2      (two products, the second on the first one's accumulators)
+// One launch, two loops, every wave takes its share of both unit lists.  The explicit loop is the shape of the unfolded Del-2
+// pass (del_fused.hip): P1's D registers - lane (r, kq) holds features 16 t + 4 kq + c of its row - ARE P2's B operand, the k
+// order of P2 is (t, c) and W2's fragments are held in that order (wr[t2][4 t + c] = W2[16 t + 4 kq + c][16 t2 + r]): no shuffle,
+// no LDS tile, h never read back.  P1's weight is too large for the registers next to W2 and comes from a 64 KB LDS image in
+// the lanes' read order (two 16-byte reads per k step, fetched a step ahead); W2 sits in a second image from which the 128
+// weight registers are loaded once per loop - the explicit order first, the listed order (wr[t][s] = W2[kq 32 + s][16 t + r])
+// after it.  As above: no branch inside a loop, rows past the end clamped to the last row, ids two units ahead, rows one unit
+// ahead (the last explicit unit requests the first listed unit's rows), a unit's out tiles stored under the next unit's matrix
+// instructions, h's tiles under P2.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void rows_gemm_select_chain_kernel(
+    const float* __restrict__ a, int64_t ld_a, const int32_t* __restrict__ idx_e, int32_t n_e, const float* __restrict__ w1,
+    const float* __restrict__ b1, float* __restrict__ pre, int64_t ld_pre, const float* __restrict__ z, int64_t ld_z,
+    const int32_t* __restrict__ idx_l, int32_t n_l, const float* __restrict__ w2, float* __restrict__ out, int64_t ld_out) {
+  constexpr int H = 128, O = 64, KQ = 32, NT1 = 8, NT2 = 4, XV = 8;
+  extern __shared__ __attribute__((aligned(16))) float wl[];
+  float* img1 = wl;                                        // W1 in read order: [s][t >> 2][lane][t & 3]
+  float* img2 = wl + H * H;                                // W2 as the kernel above keeps it: [k O + n + 16 (k / KQ)]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 15, kq = lane >> 4;
+  const int n_waves = gridDim.x * 4, wid = blockIdx.x * 4 + wave;
+  const int nu_e = (n_e + 15) >> 4, nu_l = (n_l + 15) >> 4;
+  const int e_lo = (int)((int64_t)nu_e * wid / n_waves), e_hi = (int)((int64_t)nu_e * (wid + 1) / n_waves);
+  const int l_lo = (int)((int64_t)nu_l * wid / n_waves), l_hi = (int)((int64_t)nu_l * (wid + 1) / n_waves);
+  const bool has_e = e_lo < e_hi, has_l = l_lo < l_hi;      // (wave-uniform)
+
+  auto eid = [&](int u) -> int32_t { return idx_e[min(min(u, nu_e - 1) * 16 + r, n_e - 1)]; };
+  auto lid = [&](int u) -> int32_t { return idx_l[min(min(u, nu_l - 1) * 16 + r, n_l - 1)]; };
+  auto arow = [&](int32_t row) -> const float4* { return reinterpret_cast<const float4*>(a + (int64_t)row * ld_a + kq * KQ); };
+  auto zrow = [&](int32_t row) -> const float4* { return reinterpret_cast<const float4*>(z + (int64_t)row * ld_z + kq * KQ); };
+  int32_t e_cur = eid(e_lo), e_nxt = eid(e_lo + 1);         // (n_e > 0: the host's condition)
+  int32_t l_cur = n_l > 0 ? lid(l_lo) : 0, l_nxt = n_l > 0 ? lid(l_lo + 1) : 0;
+  __builtin_amdgcn_sched_barrier(0);
+
+  // ---- the two weight images (coalesced passes over [k][n] weights), the first unit's rows in flight under them
+  float4 f1[H * H / 4 / 256], f2[H * O / 4 / 256];
+#pragma unroll
+  for (int q = 0; q < H * H / 4 / 256; ++q) f1[q] = reinterpret_cast<const float4*>(w1)[tid + 256 * q];
+#pragma unroll
+  for (int q = 0; q < H * O / 4 / 256; ++q) f2[q] = reinterpret_cast<const float4*>(w2)[tid + 256 * q];
+  __builtin_amdgcn_sched_barrier(0);
+  float4 x[XV];
+  {
+    const float4* src = (has_e || !has_l) ? arow(e_cur) : zrow(l_cur);      // (a wave without units still loads a valid row)
+#pragma unroll
+    for (int i = 0; i < XV; ++i) x[i] = src[i];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int q = 0; q < H * H / 4 / 256; ++q) {
+    const int e = tid + 256 * q, k = e / (H / 4), n4 = e % (H / 4);
+    const int s = k % KQ, t = n4 >> 2;                      // columns 4 n4 .. + 3: tile t, rows-of-the-tile 4 (n4 & 3) + j
+    float* d = img1 + ((((s * 2 + (t >> 2)) * 64) + (k / KQ) * 16 + 4 * (n4 & 3)) * 4 + (t & 3));
+    d[0] = f1[q].x; d[4] = f1[q].y; d[8] = f1[q].z; d[12] = f1[q].w;
+  }
+#pragma unroll
+  for (int q = 0; q < H * O / 4 / 256; ++q) {
+    const int e = tid + 256 * q, k = e / (O / 4), n4 = e % (O / 4);
+    *reinterpret_cast<float4*>(img2 + k * O + 4 * n4 + 16 * (k / KQ)) = f2[q];
+  }
+  __syncthreads();
+  if (!has_e && !has_l) return;
+
+  float wr[NT2][KQ];
+  const float4* wsrc = reinterpret_cast<const float4*>(img1) + lane;      // k step s: wsrc[128 s], wsrc[128 s + 64]
+  if (has_e) {
+#pragma unroll
+    for (int t2 = 0; t2 < NT2; ++t2)
+#pragma unroll
+      for (int j = 0; j < KQ; ++j) {
+        const int k = 16 * (j >> 2) + 4 * kq + (j & 3);
+        wr[t2][j] = img2[k * O + 16 * t2 + r + 16 * (k / KQ)];
+      }
+    f32x4v bz[NT1];
+#pragma unroll
+    for (int t = 0; t < NT1; ++t) {
+      const float4 b4 = *reinterpret_cast<const float4*>(b1 + 16 * t + 4 * kq);
+      bz[t] = f32x4v{b4.x, b4.y, b4.z, b4.w};
+    }
+    f32x4v acc1[NT1], acc2[NT2];
+#pragma unroll
+    for (int t = 0; t < NT2; ++t) acc2[t] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    float* dst_prev = out + (int64_t)e_cur * ld_out + 4 * kq;          // (first trip: zeros, overwritten a trip later)
+    float4 wv[2][2];
+    wv[0][0] = wsrc[0];
+    wv[0][1] = wsrc[64];
+    for (int u = e_lo; u < e_hi; ++u) {
+      const int32_t e_nn = eid(u + 2);
+      // the rows requested under P1: the next explicit unit's, or - behind the last one - the first listed unit's
+      const float4* nsrc = (u + 1 < e_hi || !has_l) ? arow(e_nxt) : zrow(l_cur);
+      float* hdst = pre + (int64_t)e_cur * ld_pre + 4 * kq;
+      // ---- P1: h = a W1 + b1
+#pragma unroll
+      for (int i = 0; i < XV; ++i) {
+        const float xv[4] = {x[i].x, x[i].y, x[i].z, x[i].w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int s = 4 * i + c;
+          wv[(s + 1) & 1][0] = wsrc[128 * ((s + 1) & (KQ - 1))];      // (s = 31: step 0 of the next unit, lands under P2)
+          wv[(s + 1) & 1][1] = wsrc[128 * ((s + 1) & (KQ - 1)) + 64];
+          const float wa[NT1] = {wv[s & 1][0].x, wv[s & 1][0].y, wv[s & 1][0].z, wv[s & 1][0].w,
+                                 wv[s & 1][1].x, wv[s & 1][1].y, wv[s & 1][1].z, wv[s & 1][1].w};
+#pragma unroll
+          for (int t = 0; t < NT1; ++t)
+            acc1[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t], xv[c], s == 0 ? bz[t] : acc1[t], 0, 0, 0);
+          if (c == 1 && (i & 1) == 0) {                      // the previous unit's out tile i / 2
+            __builtin_amdgcn_sched_barrier(0);
+            const f32x4v& o = acc2[i >> 1];
+            *reinterpret_cast<float4*>(dst_prev + 16 * (i >> 1)) = make_float4(o[0], o[1], o[2], o[3]);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        x[i] = nsrc[i];                                      // the registers just consumed: same chunk of the next unit
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // ---- P2: out = relu(h) W2 on P1's accumulators; h's tiles go out under it
+#pragma unroll
+      for (int t = 0; t < NT1; ++t) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float hv = fmaxf(acc1[t][c], 0.f);
+#pragma unroll
+          for (int t2 = 0; t2 < NT2; ++t2)
+            acc2[t2] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[t2][4 * t + c], hv, (t == 0 && c == 0) ? f32x4v{0.f, 0.f, 0.f, 0.f} : acc2[t2], 0, 0, 0);
+          if (c == 1) {
+            __builtin_amdgcn_sched_barrier(0);
+            *reinterpret_cast<float4*>(hdst + 16 * t) = make_float4(acc1[t][0], acc1[t][1], acc1[t][2], acc1[t][3]);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      dst_prev = out + (int64_t)e_cur * ld_out + 4 * kq;
+      e_cur = e_nxt;
+      e_nxt = e_nn;
+    }
+#pragma unroll
+    for (int t = 0; t < NT2; ++t) *reinterpret_cast<float4*>(dst_prev + 16 * t) = make_float4(acc2[t][0], acc2[t][1], acc2[t][2], acc2[t][3]);
+  }
+  if (!has_l) return;
+
+  // ---- the listed rows: the weight-stationary loop of rows_gemm_ws_kernel<128, 64, 0, true, false, true>
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int t = 0; t < NT2; ++t)
+#pragma unroll
+    for (int s = 0; s < KQ; ++s) wr[t][s] = img2[(kq * KQ + s) * O + 16 * t + r + 16 * kq];
+  f32x4v acc_a[NT2], acc_b[NT2];
+#pragma unroll
+  for (int t = 0; t < NT2; ++t) acc_a[t] = acc_b[t] = f32x4v{0.f, 0.f, 0.f, 0.f};
+  float* dst_prev = out + (int64_t)l_cur * ld_out + 4 * kq;
+  auto unit = [&](int u, f32x4v (&acc)[NT2], const f32x4v (&old)[NT2]) {
+    const int32_t l_nn = lid(u + 2);
+    const float4* nsrc = zrow(l_nxt);
+#pragma unroll
+    for (int i = 0; i < XV; ++i) {
+      float xv[4] = {x[i].x, x[i].y, x[i].z, x[i].w};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) xv[c] = fmaxf(xv[c], 0.f);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+#pragma unroll
+        for (int t = 0; t < NT2; ++t) {
+          if (i == 0 && c == 0) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[t][0], xv[0], f32x4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+          else acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[t][4 * i + c], xv[c], acc[t], 0, 0, 0);
+        }
+        if (c == 1) {
+          __builtin_amdgcn_sched_barrier(0);
+          if ((i & 1) == 0) *reinterpret_cast<float4*>(dst_prev + 16 * (i >> 1)) = make_float4(old[i >> 1][0], old[i >> 1][1], old[i >> 1][2], old[i >> 1][3]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      x[i] = nsrc[i];
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    dst_prev = out + (int64_t)l_cur * ld_out + 4 * kq;
+    l_cur = l_nxt;
+    l_nxt = l_nn;
+  };
+  int u = l_lo;
+  if ((l_hi - l_lo) & 1) {
+    unit(u, acc_a, acc_b);
+    ++u;
+  }
+  for (; u < l_hi; u += 2) {
+    unit(u, acc_b, acc_a);
+    unit(u + 1, acc_a, acc_b);
+  }
+#pragma unroll
+  for (int t = 0; t < NT2; ++t) *reinterpret_cast<float4*>(dst_prev + 16 * t) = make_float4(acc_a[t][0], acc_a[t][1], acc_a[t][2], acc_a[t][3]);
+}
+
+static bool select_chain_covers(int32_t n_list, int32_t n_expl, int32_t d_in, int32_t d_hid, int32_t d_out) {
+  return ws_on() && matrix_split() == 0 && n_expl > 0 && n_list >= 0 && (int64_t)n_list + n_expl >= ws_min_rows() && d_in == 128 &&
+         d_hid == 128 && d_out == 64;
+}
+
 }  // namespace gd
+
+extern "C" int gd_rows_gemm_select_chain_covers(int32_t n_list, int32_t n_expl, int32_t d_in, int32_t d_hid, int32_t d_out) {
+  return gd::select_chain_covers(n_list, n_expl, d_in, d_hid, d_out) ? 1 : 0;
+}
+
+extern "C" int gd_rows_gemm_select_chain_f32(const float* a, int64_t ld_a, const int32_t* idx_expl, int32_t n_expl, const float* w1,
+                                             const float* b1, float* pre, int64_t ld_pre, const float* z, int64_t ld_z,
+                                             const int32_t* idx_list, int32_t n_list, const float* w2, int32_t d_in, int32_t d_hid,
+                                             int32_t d_out, float* out, int64_t ld_out, void* stream) {
+  using namespace gd;
+  GD_REQUIRE(a && idx_expl && w1 && b1 && pre && w2 && out && (n_list == 0 || (z && idx_list)), GD_E_NULL,
+             "gd_rows_gemm_select_chain_f32: null pointer");
+  GD_REQUIRE(select_chain_covers(n_list, n_expl, d_in, d_hid, d_out), GD_E_DIM,
+             "gd_rows_gemm_select_chain_f32: only where gd_rows_gemm_select_chain_covers(n_list=%d, n_expl=%d, %d, %d, %d) holds", n_list,
+             n_expl, d_in, d_hid, d_out);
+  GD_REQUIRE(ld_a >= d_in && ld_pre >= d_hid && ld_z >= d_hid && ld_out >= d_out && ld_a % 4 == 0 && ld_pre % 4 == 0 && ld_z % 4 == 0 &&
+                 ld_out % 4 == 0,
+             GD_E_DIM, "gd_rows_gemm_select_chain_f32: row pitches must hold a row and be multiples of 4 floats");
+  GD_REQUIRE(aligned16(a) && aligned16(w1) && aligned16(b1) && aligned16(pre) && aligned16(w2) && aligned16(out) && (!z || aligned16(z)),
+             GD_E_DIM, "gd_rows_gemm_select_chain_f32: 16-byte aligned buffers required");
+  GD_REQUIRE(out != a && out != pre && out != z && pre != a && pre != z, GD_E_DIM,
+             "gd_rows_gemm_select_chain_f32: out and pre must not alias each other or an input");
+  constexpr size_t lds = (size_t)(128 * 128 + 128 * 64 + 64) * sizeof(float);
+  static const hipError_t once = hipFuncSetAttribute((const void*)rows_gemm_select_chain_kernel,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  GD_REQUIRE(once == hipSuccess, -(int)once, "gd_rows_gemm_select_chain_f32: cannot raise the LDS limit");
+  hipLaunchKernelGGL(rows_gemm_select_chain_kernel, dim3(ws_cu_count()), dim3(256), lds, (hipStream_t)stream, a, ld_a, idx_expl,
+                     n_expl, w1, b1, pre, ld_pre, z, ld_z, idx_list, n_list, w2, out, ld_out);
+  return launched("rows_gemm_select_chain");
+}
 
 extern "C" int gd_rows_gemm_accumulate_f32(const float* in, int64_t ld_in, const int32_t* idx, int32_t n_sel, const float* w,
                                            int32_t d_in, int32_t d_out, int32_t trans_w, float* out, int64_t ld_out, void* stream) {

@@ -33,7 +33,9 @@ One decision rides on top of the forms: plan_del2_fold(facts, forms, covers, ena
 GCN / GIN step folds W_D2 into conv2's weight (the Del-2 pass stores dz2 and W_D2^T W2 instead of forming dz2 W_D2^T per row).
 A second one of the same kind, plan_layer1_fold(facts, forms, covers, enabled): whether the chained GCN step folds conv1's weight
 into W_D1 - the step aggregates x itself (a = A^ x), the chained Del-1 pass takes a and W1^T W_D1, and a W1^T + b1 is formed only on
-the rows outside the Del-1 mask, the only rows whose conv1 output anything reads.
+the rows outside the Del-1 mask, the only rows whose conv1 output anything reads.  On top of that, plan_explicit_chain(facts, forms,
+covers, enabled, fold1=..., n_explicit=...): whether those rows are formed inside conv2's Linear launch, their only reader, instead of
+in a launch of their own.
 """
 import os
 import warnings
@@ -192,6 +194,23 @@ def plan_layer1_fold(facts, forms, covers, enabled=True):
     128 x 128 - the input width is the engine's to check, StepFacts does not carry it."""
     return bool(enabled and covers and forms.chain1 and forms.fuse_del1 and forms.split1 and facts.mode == 'gcn'
                 and facts.loss_type == 'both_layerwise' and not facts.cache_layer1 and facts.h == 128)
+
+
+def read_explicit_chain(env=None):
+    """GD_EXPLICIT_CHAIN (default on; 0 = conv1's explicit rows in a launch of their own, for A/B runs).  Read once per construction;
+    not a Knobs field, like GD_LAYER1_FOLD."""
+    env = os.environ if env is None else env
+    return env.get('GD_EXPLICIT_CHAIN') != '0'
+
+
+def plan_explicit_chain(facts, forms, covers, enabled=True, *, fold1, n_explicit):
+    """Does the folded GCN step form conv1's output on its explicit rows (the rows outside S1) INSIDE conv2's Linear launch
+    (gd_rows_gemm_select_chain_f32: h = a W1^T + b1 stored to pre1, relu(h) W2^T taken from the same accumulators) instead of in a
+    launch of its own whose only reader is that Linear?  Pure.  Only for the full folded step (fold1 = what plan_layer1_fold said;
+    the rows-only step lists S2 rows and keeps its two launches, a cached layer 1 never folds) at 128 -> 128 -> 64, where there are
+    explicit rows at all.  covers: gd_rows_gemm_select_chain_covers(s1, n_explicit, 128, h, o)."""
+    return bool(enabled and covers and fold1 and facts.mode == 'gcn' and not forms.rows_only and not facts.cache_layer1
+                and facts.h == 128 and facts.o == 64 and n_explicit > 0)
 
 
 def _loss_coefficients(loss_type, alpha):
@@ -769,6 +788,12 @@ class NodeembEngine:
             rest[self.idx1.long()] = False
             self._idx1c = rest.nonzero().flatten().to(torch.int32)
             self.pre1.zero_()
+        # _chain_expl (plan_explicit_chain): a W1^T + b1 on the rows of _idx1c is formed by the launch that reads it - conv2's Linear
+        # (_linear_relu_z1) - and stored to pre1 from there; _conv1_forward stops after the aggregation
+        self._chain_expl = plan_explicit_chain(
+            self.facts, self.forms,
+            self._fold1 and bool(lib.gd_rows_gemm_select_chain_covers(self.s1, int(self._idx1c.numel()), x.shape[1], self.h, self.o)),
+            read_explicit_chain(), fold1=self._fold1, n_explicit=int(self._idx1c.numel()) if self._fold1 else 0)
         self._gat_r1 = None                                           # (att_src W2, att_dst W2): constants of the frozen conv2
         if self._mode == 'gat':
             w2_ = conv2.lin_src.weight.detach()
@@ -873,6 +898,9 @@ class NodeembEngine:
         """relu(z1) @ weight^T where z1 = Del-1 output on the S1 rows and conv1 output elsewhere (idx / out: as _linear)."""
         if not self._split1:       # (layer 1 cached: z1 holds conv1's output with the Del'd rows written over it)
             return self._linear(self.z1, weight, relu_in=True, idx=idx, out=out)
+        if self._chain_expl:       # (full folded GCN step: S1 rows from z1, the rest formed from a = A^ x here and left in pre1)
+            assert idx is None
+            return ops.rows_gemm_select_chain(self._a1, self._idx1c, self._w1, self._b1, self.pre1, self.z1, self.idx1, weight, out=out)
         if idx is not None or self._mfma_weight(weight):
             return ops.rows_gemm_select(self.pre1, self.z1, self._sel1, weight, trans_w=True, const_w=True, relu_in=True,
                                         out=out, idx=idx)
@@ -896,7 +924,7 @@ class NodeembEngine:
             # a = A^ x (the rows-only step: on the S2 rows; x is complete, so no transformed buffer and no closure condition here),
             # then conv1's output on the rows outside S1 alone
             self._spmm(False, g.val, self.x, self._a1, None, 0.0, plan=self._plan2 if self._rows_only else None)
-            if self._idx1c.numel():
+            if self._idx1c.numel() and not self._chain_expl:          # (_chain_expl: formed where conv2's Linear reads it)
                 ops.rows_gemm(self._a1, self._idx1c, self._w1, trans_w=True, const_w=True, bias=self._b1, out=self.pre1)
         elif self._mode == 'gcn':
             idx, out, plan = self._layer1_rows(c.lin.weight)

@@ -270,6 +270,33 @@ def rows_gemm_select(inp, inp_alt, sel, w, trans_w=False, bias=None, relu_in=Fal
     return out
 
 
+def rows_gemm_select_chain_ok(n_list, n_expl, d_in, d_hid, d_out):
+    """Does gd_rows_gemm_select_chain_f32 take these sizes (128 -> 128 -> 64, explicit rows, the weight-stationary row range)?"""
+    return bool(_lib.lib().gd_rows_gemm_select_chain_covers(int(n_list), int(n_expl), int(d_in), int(d_hid), int(d_out)))
+
+
+def rows_gemm_select_chain(a, idx_expl, w1, b1, pre, z, idx_list, w2, out=None):
+    """conv2's Linear where conv1's output exists on the listed rows only (raw, no autograd): gd_rows_gemm_select_chain_f32.
+      listed row r (idx_list):   out[r] = relu(z[r]) @ w2^T
+      explicit row r (idx_expl): pre[r] = a[r] @ w1^T + b1, out[r] = relu(pre[r]) @ w2^T
+    w1 [d_hid, d_in], w2 [d_out, d_hid]: Linear weights, constant across calls (see _const_weight); the lists are int32, sorted and
+    disjoint.  Only where rows_gemm_select_chain_ok says yes - there is no other form behind this call."""
+    a, z = _f32_rows(a), _f32_rows(z)
+    w1t, w2t = _const_weight(w1, True)[0], _const_weight(w2, True)[0]
+    d_in, d_hid, d_out = int(w1t.shape[0]), int(w1t.shape[1]), int(w2t.shape[1])
+    assert a.shape[1] == d_in and z.shape[1] == d_hid and w2t.shape[0] == d_hid and b1.numel() == d_hid
+    assert pre.dtype == torch.float32 and pre.stride(1) == 1 and pre.shape[1] == d_hid
+    assert idx_expl.dtype == torch.int32 and idx_list.dtype == torch.int32
+    if out is None:
+        out = torch.empty(z.shape[0], d_out, dtype=torch.float32, device=z.device)
+    assert out.dtype == torch.float32 and out.stride(1) == 1 and out.shape[1] == d_out
+    check(_lib.lib().gd_rows_gemm_select_chain_f32(ptr(a), a.stride(0), ptr(idx_expl), int(idx_expl.shape[0]), ptr(w1t), ptr(b1),
+                                                   ptr(pre), pre.stride(0), ptr(z), z.stride(0), ptr(idx_list),
+                                                   int(idx_list.shape[0]), ptr(w2t), d_in, d_hid, d_out, ptr(out), out.stride(0),
+                                                   stream_ptr(a.device)), 'gd_rows_gemm_select_chain_f32')
+    return out
+
+
 def rows_gemm_accumulate_ok(n_rows, d_in, d_out):
     """Does gd_rows_gemm_accumulate_f32 take this shape (the weight-stationary form's: widths in {64, 128}, >= 65,536 rows)?"""
     return matrix_split() == 0 and bool(_lib.lib().gd_rows_gemm_ws_covers(int(n_rows), int(d_in), int(d_out)))

@@ -62,6 +62,8 @@ extern "C" {
                                 gd_eval_triple_scores_f32 (+ its _workspace query): the same for the knowledge-graph trainers' DistMult
                                 triples (entries added: the version stays);
                                 gd_subset_rank_metrics_drawn, gd_subset_draw: the 500 validation subsets drawn inside the rank kernel
+                                (entries added: the version stays);
+                                gd_rows_gemm_select_chain_f32 (+ its _covers query): conv1's explicit rows formed inside conv2's Linear
                                 (entries added: the version stays) */
 
 enum {
@@ -502,6 +504,21 @@ int gd_rows_gemm_select_f32(const float* in, const float* in_alt, const uint8_t*
                             const int32_t* idx, int32_t n_sel, const float* w, int32_t d_in, int32_t d_out,
                             int32_t trans_w, const float* bias, int32_t relu_in,
                             float* out, int64_t ld_out, void* stream);
+
+/* conv2's Linear over a layer-1 output of which only the Del-1 rows exist (the step with conv1's weight folded into W_D1), in
+ * one weight-stationary launch:
+ *   listed row   r = idx_list[s]:  out[r,:] = relu(z[r,:]) @ W2                 - bit-equal to gd_rows_gemm_select_f32 on that row
+ *   explicit row r = idx_expl[s]:  h = a[r,:] @ W1 + b1, pre[r,:] = h, out[r,:] = relu(h) @ W2
+ * (the second product takes the first one's accumulators: h is stored for whoever reads conv1's output, never read back).
+ * W1 [d_in, d_hid] and W2 [d_hid, d_out] are k-major ([k][n]: a Linear's weight transposed); the two lists are disjoint and
+ * sorted; every pitch is a multiple of 4 floats, every buffer 16-byte aligned, out / pre alias nothing.  Only where
+ * gd_rows_gemm_select_chain_covers holds: 128 -> 128 -> 64, n_expl > 0, n_list + n_expl >= 65,536 (the weight-stationary range),
+ * no split arithmetic; GD_E_DIM otherwise (the caller then keeps gd_rows_gemm_f32 + gd_rows_gemm_select_f32). */
+int gd_rows_gemm_select_chain_covers(int32_t n_list, int32_t n_expl, int32_t d_in, int32_t d_hid, int32_t d_out);
+int gd_rows_gemm_select_chain_f32(const float* a, int64_t ld_a, const int32_t* idx_expl, int32_t n_expl, const float* w1,
+                                  const float* b1, float* pre, int64_t ld_pre, const float* z, int64_t ld_z,
+                                  const int32_t* idx_list, int32_t n_list, const float* w2, int32_t d_in, int32_t d_hid,
+                                  int32_t d_out, float* out, int64_t ld_out, void* stream);
 
 /* (ABI 9) out[r,:] += in[r,:] @ (trans_w ? W^T : W) for r = idx[s] or s, s < n_sel - the weight-stationary form with the
  * accumulators of a 16-row unit started from the rows of `out` (fetched a unit ahead).  GraphSAGE's root term: SAGEConv is

@@ -6,7 +6,8 @@ guide: FETCH_SIZE counts 32 B per request where the 16-B/lane gathers move 64 ->
 
   python tools/rocpd_stage_table.py kt.db [--fetch f.db] [--write w.db] [--marker loss_finalize] [--out stages.json]
         [--stages name,name,...]   (labels by position; default = the GCN both_layerwise step with GD_LAYER1_FOLD=0; 'fold1' = the same
-                                    step with conv1's weight folded into W_D1; 'auto' = k00, k01, ... for any step)
+                                    step with conv1's weight folded into W_D1 and GD_EXPLICIT_CHAIN=0; 'chain' = the folded step of
+                                    seven launches, conv1's explicit rows formed inside t2; 'auto' = k00, k01, ... for any step)
 """
 import argparse
 import json
@@ -15,6 +16,8 @@ import sqlite3
 GCN_STEP = ['xw1', 'spmm1', 'del1_loss_wgrad1', 't2', 'spmm2', 'del2_loss_bwd', 'spmm2_t', 'tail']          # (chained Del-1 pass: dh is formed in it)
 GCN_STEP_FOLD1 = ['spmm1', 'pre1_rest', 'del1_loss_wgrad1', 't2', 'spmm2', 'del2_loss_bwd', 'spmm2_t', 'tail']   # (conv1's weight folded into W_D1:
 #   spmm1 aggregates x itself, pre1_rest = a W1^T + b1 on the rows outside the Del-1 mask; pass --stages with this list)
+GCN_STEP_CHAIN = ['spmm1', 'del1_loss_wgrad1', 't2', 'spmm2', 'del2_loss_bwd', 'spmm2_t', 'tail']   # (seven launches: the folded step with
+#   pre1_rest formed inside t2, gd_rows_gemm_select_chain_f32; --stages chain)
 GCN_STEP_R05A = ['xw1', 'spmm1', 'del1_loss_wgrad1', 't2', 'spmm2', 'del2_loss_bwd', 'spmm2_t', 'dh', 'tail']   # (GD_DEL1_CHAIN=0)
 GCN_STEP_R04 = ['xw1', 'spmm1', 'del1', 'wgrad1', 't2', 'spmm2', 'del2_loss_bwd', 'spmm2_t', 'dh', 'tail']     # (GD_DEL1_FUSED=0: two launches)
 
@@ -45,7 +48,7 @@ def main():
     rows = kernels(a.db)
     marks = [i for i, r in enumerate(rows) if a.marker in r[0]]
     steps = [rows[marks[j] + 1: marks[j + 1] + 1] for j in range(len(marks) - 1)]
-    labels = GCN_STEP_FOLD1 if a.stages == 'fold1' else a.stages.split(',')
+    labels = {'fold1': GCN_STEP_FOLD1, 'chain': GCN_STEP_CHAIN}.get(a.stages) or a.stages.split(',')
     if a.stages == 'auto':              # any step: the most frequent kernel count between two markers, labels by position
         from collections import Counter
         k = Counter(len(s) for s in steps[a.skip:]).most_common(1)[0][0]
