@@ -38,6 +38,10 @@ class SplitPlan:
             lo, hi = (0, rowptr.numel() - 1) if row_range is None else row_range
             ids = torch.arange(lo, hi, device=dev)
         r_start, r_end = rpl[ids], rpl[ids + 1]
+        self._outside = None
+        if rows is not None or row_range is not None:
+            self._outside = torch.ones(rowptr.numel() - 1, dtype=torch.bool, device=dev)
+            self._outside[ids] = False
         n = ids.numel()
         deg = r_end - r_start
         pieces = torch.clamp((deg + chunk - 1) // chunk, min=1)
@@ -346,6 +350,11 @@ class SplitPlan:
         hit = (items, total, torch.tensor(bounds, dtype=torch.int32, device=dev), tags)
         self._onepass[key] = hit
         return hit
+
+    def rows_outside(self):
+        """bool [rows of the CSR]: True on the rows that are NOT in the plan, None for a plan over every row (built with the
+        plan, ahead of any capture)."""
+        return self._outside
 
     def scratch_flat(self, tag, n_floats, device):
         """Named flat work buffers (e.g. the GAT kernels' merge scratch), kept per plan."""

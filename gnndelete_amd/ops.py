@@ -683,6 +683,10 @@ def gat_backward_raw(graph, h, a_src, a_dst, rowmax, rowsum, dy, slope, plan=Non
     alpha_t = _ws_buf(bufs, 'alpha_t', (g.nnz,), dev)
     check(_lib.lib().gd_gat_transpose_edges_f32(ptr(g.rowptr_t), ptr(g.perm_t), ptr(ade), n, ptr(alpha_t),
                                                 ptr(da_src), stream_ptr(dev)), 'gd_gat_transpose_edges_f32')
+    if plan_t is not None and plan_t.rows_outside() is not None:
+        # the transposition pass sums every source row; rows outside the subset are not produced: zero, as the form above
+        # leaves them (tests/test_gat_kernels_gpu.py, section D)
+        da_src.masked_fill_(plan_t.rows_outside(), 0.0)
     # (the item kernel gd_spmm_csr_onepass_aux_f32 sweeps with: this path is its reference, the same sums bit for bit)
     dh = _spmm_raw(g.rowptr_t, g.col_t, alpha_t, dy, None, 0.0, n, pt, out=dh, wide=False)
     return dh, da_src, da_dst
