@@ -118,6 +118,10 @@ PROTOTYPES = {
     'gd_layer1_fold_f32': (ctypes.c_int, [_p, _p, _p, _p, _p, _p]),
     'gd_step_tail_fold1_f32': (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p,
                                               _f64, _f64, _f64, _f64, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p]),
+    'gd_spmm_csr_onepass_wide_hosted_f32': (ctypes.c_int, [_p, _i32, _p, _p, _p, _i64, _p, _i64, _p, _f32, _p, _i32, _i32, _i32, _p,
+                                                           _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                                           _p, _i32, _i32, _i32, _p, _p, _p, _p, _f64, _f64, _f64, _f64,
+                                                           _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p]),
     'gd_del1_loss_wgrad_f32': (ctypes.c_int, [_p, _i64, _p, _i32, _p, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _i32, _p]),
     'gd_rowtarget_mse_blocks': (_i32, [_i32]),
     'gd_rowfold_loss_blocks': (_i32, [_i32]),

@@ -13,6 +13,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "tail_jobs.h"
 
 namespace gd {
 
@@ -468,17 +469,19 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 #define GD_SPMM_WIDE_GRID_CAP 8192
 #endif
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void spmm_wide_kernel(
+// The sweep is a device function of the block's index `bid` among the `nblk` sweep blocks: spmm_wide_kernel calls it with blockIdx.x
+// and gridDim.x, spmm_wide_hosted_kernel (below it) behind the blocks that run the step tail's jobs.
+__device__ __forceinline__ void spmm_wide_body(
     const int4* __restrict__ items, int32_t n_items, const int32_t* __restrict__ xcd_bounds, const int32_t* __restrict__ colt,
     const float* __restrict__ val, const float* __restrict__ x, int64_t ldx, float* __restrict__ y, int64_t ldy,
-    const float* __restrict__ bias, float self_coef, const float* __restrict__ xs, int32_t nnz) {
+    const float* __restrict__ bias, float self_coef, const float* __restrict__ xs, int32_t nnz, uint32_t bid, uint32_t nblk) {
   constexpr int kXcd = 8, U = 4;
   constexpr int kSrcMask = (1 << 24) - 1;
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4, li = lane & 15;
-  const int xcd = blockIdx.x % kXcd;
-  const int stride = (gridDim.x / kXcd) * 4;                        // waves per XCD
-  const int wx = (blockIdx.x / kXcd) * 4 + (threadIdx.x >> 6);
+  const int xcd = bid % kXcd;
+  const int stride = (nblk / kXcd) * 4;                             // waves per XCD
+  const int wx = (bid / kXcd) * 4 + (threadIdx.x >> 6);
   const int i0 = xcd_bounds[xcd], i1 = xcd_bounds[xcd + 1];
   // (the barrier invariant of the group path, checked where it costs the sweep no register: spmm_persist_body)
   if ((i0 | i1) & 3) __builtin_trap();
@@ -649,6 +652,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     d0 = d1;
     d1 = d2;
   }
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void spmm_wide_kernel(
+    const int4* __restrict__ items, int32_t n_items, const int32_t* __restrict__ xcd_bounds, const int32_t* __restrict__ colt,
+    const float* __restrict__ val, const float* __restrict__ x, int64_t ldx, float* __restrict__ y, int64_t ldy,
+    const float* __restrict__ bias, float self_coef, const float* __restrict__ xs, int32_t nnz) {
+  spmm_wide_body(items, n_items, xcd_bounds, colt, val, x, ldx, y, ldy, bias, self_coef, xs, nnz, blockIdx.x, gridDim.x);
+}
+
+// gd_spmm_csr_onepass_wide_hosted_f32: the launch carries the step tail's jobs in front of the sweep.  The first host.nh blocks of
+// the grid (a multiple of 8, so that the sweep blocks' XCD residues and xcd_bounds ranges are the unhosted launch's) run
+// tail_host_block and return; every sweep block is block blockIdx.x - nh of gridDim.x - nh.  The sweep is fabric-bound with 8 small
+// blocks per CU: a few hundred short blocks that start first disappear in it, and the step loses the tail's launch.  No block of
+// either kind waits for another.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void spmm_wide_hosted_kernel(
+    const int4* __restrict__ items, int32_t n_items, const int32_t* __restrict__ xcd_bounds, const int32_t* __restrict__ colt,
+    const float* __restrict__ val, const float* __restrict__ x, int64_t ldx, float* __restrict__ y, int64_t ldy,
+    const float* __restrict__ bias, float self_coef, const float* __restrict__ xs, int32_t nnz, TailHost host) {
+  if (blockIdx.x < (uint32_t)host.nh) {
+    tail_host_block(host, (int)blockIdx.x);
+    return;
+  }
+  spmm_wide_body(items, n_items, xcd_bounds, colt, val, x, ldx, y, ldy, bias, self_coef, xs, nnz, blockIdx.x - host.nh, gridDim.x - host.nh);
 }
 
 __global__ __launch_bounds__(256) void spmm_fixup_kernel(const int4* __restrict__ split, int32_t n_split,
@@ -896,32 +922,87 @@ extern "C" int gd_spmm_csr_onepass_f32(const int32_t* items, int32_t n_items, co
                         xcd_bounds, (hipStream_t)stream);
 }
 
-extern "C" int gd_spmm_csr_onepass_wide_f32(const int32_t* items, int32_t n_items, const int32_t* col_tagged, const float* val,
-                                            const float* x, int64_t ldx, float* y, int64_t ldy, const float* bias,
-                                            float self_coef, const float* x_self, int32_t d, int32_t nnz, int32_t x_rows,
-                                            const int32_t* xcd_bounds, void* stream) {
-  using namespace gd;
-  GD_REQUIRE(col_tagged && x && y && xcd_bounds && (items || n_items == 0), GD_E_NULL, "gd_spmm_csr_onepass_wide_f32: null pointer");
+namespace gd {
+// the wide launch, with the tail's jobs in front of the sweep where `host` is given (n_items > 0 then)
+static int launch_wide(const char* name, const int32_t* items, int32_t n_items, const int32_t* col_tagged, const float* val, const float* x,
+                       int64_t ldx, float* y, int64_t ldy, const float* bias, float self_coef, const float* x_self, int32_t d,
+                       int32_t nnz, int32_t x_rows, const int32_t* xcd_bounds, const TailHost* host, void* stream) {
+  GD_REQUIRE(col_tagged && x && y && xcd_bounds && (items || n_items == 0), GD_E_NULL, "%s: null pointer", name);
   GD_REQUIRE(n_items >= 0 && n_items % 4 == 0 && d == 64 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= d && ldy >= d, GD_E_DIM,
-             "gd_spmm_csr_onepass_wide_f32: d must be 64 (got %d) with 16-byte row strides, n_items a multiple of 4", d);
-  GD_REQUIRE(aligned16(x) && aligned16(y) && aligned16(items) && (!bias || aligned16(bias)), GD_E_ALIGN,
-             "gd_spmm_csr_onepass_wide_f32: unaligned pointer");
-  GD_REQUIRE(x != y, GD_E_DIM, "gd_spmm_csr_onepass_wide_f32: x and y must not alias");
+             "%s: d must be 64 (got %d) with 16-byte row strides, n_items a multiple of 4", name, d);
+  GD_REQUIRE(aligned16(x) && aligned16(y) && aligned16(items) && (!bias || aligned16(bias)), GD_E_ALIGN, "%s: unaligned pointer", name);
+  GD_REQUIRE(x != y, GD_E_DIM, "%s: x and y must not alias", name);
   GD_REQUIRE(x_rows > 0 && x_rows < (1 << 24) && ldx * 4 < (1 << 24) && ldy * 4 < (1 << 24) &&
                  (int64_t)x_rows * ldx * 4 < (1ll << 32) && (int64_t)x_rows * ldy * 4 < (1ll << 32), GD_E_DIM,
-             "gd_spmm_csr_onepass_wide_f32: x and y must be smaller than 4 GiB with row ids and pitches below 2^24");
+             "%s: x and y must be smaller than 4 GiB with row ids and pitches below 2^24", name);
+  GD_REQUIRE(!host || n_items > 0, GD_E_DIM, "%s: the tail's jobs need a launch to ride on (n_items = 0)", name);
   if (n_items == 0) return GD_OK;
   const float* xs = x_self ? x_self : x;
-  GD_REQUIRE(aligned16(xs) && xs != y, GD_E_ALIGN, "gd_spmm_csr_onepass_wide_f32: bad x_self");
+  GD_REQUIRE(aligned16(xs) && xs != y, GD_E_ALIGN, "%s: bad x_self", name);
   const char* e = getenv("GD_SPMM_GRID_CAP");               // tuning knob (blocks)
   const int cap_env = e ? atoi(e) : 0;
   const int cap = cap_env > 0 ? cap_env : GD_SPMM_WIDE_GRID_CAP;
   int nblk = (n_items + 3) / 4;
   if (nblk > cap) nblk = cap;
   nblk = (nblk + 7) / 8 * 8;
+  if (host) {
+    hipLaunchKernelGGL(spmm_wide_hosted_kernel, dim3(host->nh + nblk), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const int4*>(items), n_items, xcd_bounds, col_tagged, val, x, ldx, y, ldy, bias, self_coef, xs, nnz,
+                       *host);
+    return launched("spmm_wide_hosted");
+  }
   hipLaunchKernelGGL(spmm_wide_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const int4*>(items), n_items,
                      xcd_bounds, col_tagged, val, x, ldx, y, ldy, bias, self_coef, xs, nnz);
   return launched("spmm_wide");
+}
+}  // namespace gd
+
+extern "C" int gd_spmm_csr_onepass_wide_f32(const int32_t* items, int32_t n_items, const int32_t* col_tagged, const float* val,
+                                            const float* x, int64_t ldx, float* y, int64_t ldy, const float* bias,
+                                            float self_coef, const float* x_self, int32_t d, int32_t nnz, int32_t x_rows,
+                                            const int32_t* xcd_bounds, void* stream) {
+  return gd::launch_wide("gd_spmm_csr_onepass_wide_f32", items, n_items, col_tagged, val, x, ldx, y, ldy, bias, self_coef, x_self, d, nnz,
+                         x_rows, xcd_bounds, nullptr, stream);
+}
+
+extern "C" int gd_spmm_csr_onepass_wide_hosted_f32(
+    const int32_t* items, int32_t n_items, const int32_t* col_tagged, const float* val, const float* x, int64_t ldx, float* y, int64_t ldy,
+    const float* bias, float self_coef, const float* x_self, int32_t d, int32_t nnz, int32_t x_rows, const int32_t* xcd_bounds,
+    const float* partials1_t, const float* colsum1, int32_t n_part1, int32_t d1, const float* w1, const float* w1_t, const float* b1,
+    float* dw1, float* param1, float* exp_avg1, float* exp_avg_sq1, float* w_fold, float* bias_fold, const float* partials2,
+    int32_t n_part2, int32_t d2, int32_t accumulate2, float* dw2, float* param2, float* exp_avg2, float* exp_avg_sq2, double lr,
+    double beta1, double beta2, double eps, const float* loss_partials1, int32_t n1, const float* loss_partials2, int32_t n2, float* hist,
+    int32_t capacity, int32_t* pos, int32_t* iter, int32_t* arrive, void* stream) {
+  using namespace gd;
+  const char* name = "gd_spmm_csr_onepass_wide_hosted_f32";
+  GD_REQUIRE(n_part1 >= 0 && n_part2 >= 0 && n_part1 + n_part2 > 0, GD_E_DIM,
+             "%s: a hosted launch carries job 1, job 2 or both (partial counts %d, %d)", name, n_part1, n_part2);
+  GD_REQUIRE(iter, GD_E_NULL, "%s: null iteration counter", name);
+  TailHost h{};
+  h.lr = lr; h.beta1 = beta1; h.beta2 = beta2; h.eps = eps;
+  h.fin = TailFin{loss_partials1, n1, loss_partials2, n2, hist, capacity, pos, iter, arrive};
+  if (n_part1 > 0) {
+    GD_REQUIRE(partials1_t && colsum1 && w1 && w1_t && b1 && dw1 && param1 && exp_avg1 && exp_avg_sq1 && w_fold && bias_fold, GD_E_NULL,
+               "%s: null pointer of job 1", name);
+    GD_REQUIRE(d1 == 128, GD_E_DIM, "%s: the folded layer-1 job is 128 wide (d1=%d)", name, d1);
+    GD_REQUIRE(aligned16(partials1_t), GD_E_ALIGN, "%s: unaligned partials of job 1", name);
+    h.j1 = TailJob{partials1_t, n_part1, d1 * d1, 0, dw1, param1, exp_avg1, exp_avg_sq1};
+    h.fo = TailFold1{colsum1, w1, b1, w_fold, bias_fold};
+    h.w1t = w1_t;
+    h.n1b = 128;
+  }
+  if (n_part2 > 0) {
+    GD_REQUIRE(partials2 && dw2 && param2 && exp_avg2 && exp_avg_sq2, GD_E_NULL, "%s: null pointer of job 2", name);
+    GD_REQUIRE(hist && pos && arrive && capacity > 0 && n1 >= 0 && n2 >= 0 && (n1 == 0 || loss_partials1) && (n2 == 0 || loss_partials2),
+               GD_E_NULL, "%s: null bookkeeping pointer", name);
+    GD_REQUIRE(d2 > 0 && d2 % 4 == 0 && d2 <= 128, GD_E_DIM, "%s: d2=%d must be a multiple of 4, at most 128", name, d2);
+    GD_REQUIRE(aligned16(partials2) && aligned16(dw2) && aligned16(param2) && aligned16(exp_avg2) && aligned16(exp_avg_sq2), GD_E_ALIGN,
+               "%s: unaligned pointer of job 2", name);
+    h.j2 = TailJob{partials2, n_part2, d2 * d2, accumulate2, dw2, param2, exp_avg2, exp_avg_sq2};
+    h.nb2 = (h.j2.n_elem / 4 + 15) / 16;
+  }
+  h.nh = (h.n1b + h.nb2 + 7) / 8 * 8;
+  return launch_wide(name, items, n_items, col_tagged, val, x, ldx, y, ldy, bias, self_coef, x_self, d, nnz, x_rows, xcd_bounds, &h, stream);
 }
 
 extern "C" int gd_spmm_csr_onepass_aux_f32(const int32_t* items, int32_t n_items, const int32_t* col, const int32_t* perm,

@@ -35,7 +35,8 @@ A second one of the same kind, plan_layer1_fold(facts, forms, covers, enabled): 
 into W_D1 - the step aggregates x itself (a = A^ x), the chained Del-1 pass takes a and W1^T W_D1, and a W1^T + b1 is formed only on
 the rows outside the Del-1 mask, the only rows whose conv1 output anything reads.  On top of that, plan_explicit_chain(facts, forms,
 covers, enabled, fold1=..., n_explicit=...): whether those rows are formed inside conv2's Linear launch, their only reader, instead of
-in a launch of their own.
+in a launch of their own.  And plan_tail_hosted(facts, forms, enabled, fold1=..., fold2=..., wide=..., padded=...): whether the tail's
+jobs ride on the two layer-2 aggregation launches instead of a launch of their own (six launches; step_stages() lists them).
 """
 import os
 import warnings
@@ -211,6 +212,27 @@ def plan_explicit_chain(facts, forms, covers, enabled=True, *, fold1, n_explicit
     explicit rows at all.  covers: gd_rows_gemm_select_chain_covers(s1, n_explicit, 128, h, o)."""
     return bool(enabled and covers and fold1 and facts.mode == 'gcn' and not forms.rows_only and not facts.cache_layer1
                 and facts.h == 128 and facts.o == 64 and n_explicit > 0)
+
+
+def read_tail_hosted(env=None):
+    """GD_TAIL_HOSTED (default on; 0 = the tail in a launch of its own, seven launches, for A/B runs).  Read once per construction;
+    not a Knobs field, like GD_EXPLICIT_CHAIN."""
+    env = os.environ if env is None else env
+    return env.get('GD_TAIL_HOSTED') != '0'
+
+
+def plan_tail_hosted(facts, forms, enabled=True, *, fold1, fold2, wide, padded):
+    """Do the tail's jobs ride on the two layer-2 aggregation launches (gd_spmm_csr_onepass_wide_hosted_f32) instead of a launch of
+    their own - six launches instead of seven?  Pure.  W_D1's job reads only what the Del-1 pass of the same step left and writes
+    what the Del-1 pass of the NEXT step reads, so it goes with the forward aggregation; W_D2's job and the loss finalize read what
+    the Del-2 pass left and go with the transposed one.  Only for the chained GCN step folded in both layers (fold1 / fold2 = what
+    plan_layer1_fold / plan_del2_fold said) with the layer-wise update and the tail launch, on every row (the rows-only step
+    aggregates under other plans), where both aggregations run the wide 64-float form (wide = ops.spmm_wide_form of their shapes:
+    the d = 128 sweep and the weight-stationary passes fill a compute unit, extra blocks would queue behind theirs), without a
+    padded class dimension (its copy-back follows the tail).  NodeembEngine alone asks: PartitionedNodeembEngine builds its own
+    step and never hosts."""
+    return bool(enabled and fold1 and fold2 and forms.tail and forms.chain1 and forms.fuse_wg2 and facts.mode == 'gcn'
+                and facts.loss_type == 'both_layerwise' and not forms.rows_only and wide and not padded)
 
 
 def _loss_coefficients(loss_type, alpha):
@@ -794,7 +816,15 @@ class NodeembEngine:
             self.facts, self.forms,
             self._fold1 and bool(lib.gd_rows_gemm_select_chain_covers(self.s1, int(self._idx1c.numel()), x.shape[1], self.h, self.o)),
             read_explicit_chain(), fold1=self._fold1, n_explicit=int(self._idx1c.numel()) if self._fold1 else 0)
-        self._gat_r1 = None                                           # (att_src W2, att_dst W2): constants of the frozen conv2
+        # _tail_hosted (plan_tail_hosted): no tail launch - W_D1's job rides on the forward layer-2 aggregation, W_D2's job and the
+        # loss finalize on the transposed one.  _w1t: W1^T, the operand of dW[:, c] = W1 G[:, c] read from global memory there
+        # (constant like _w1; this engine owns it, so a captured graph's address stays valid)
+        self._tail_hosted = plan_tail_hosted(
+            self.facts, self.forms, read_tail_hosted(), fold1=self._fold1, fold2=self._fold2,
+            wide=ops.spmm_wide_form(self.o, n, self.o, self.o), padded=self._user_wd2 is not None)
+        if self._tail_hosted:
+            self._w1t = self._w1.t().contiguous()
+        self._gat_r1 = None                                          # (att_src W2, att_dst W2): constants of the frozen conv2
         if self._mode == 'gat':
             w2_ = conv2.lin_src.weight.detach()
             self._gat_r1 = ((conv2.att_src.detach().reshape(1, -1) @ w2_).reshape(-1).float().contiguous(),
@@ -992,7 +1022,9 @@ class NodeembEngine:
             # relu(z1) @ W2^T, then the aggregation: on the S2 rows into the fixed buffer under the rows-only plan, or on every row
             idx, out, plan = (self.idx2, self._t2buf, self._plan2) if self._rows_only else (None, None, None)
             if self._mode == 'gcn':
-                self._spmm(False, self.graph.val, self._linear_relu_z1(c.lin.weight, idx, out), self.p2, c.bias, 0.0, plan=plan)
+                # (_tail_hosted: this launch carries W_D1's job of the tail)
+                self._spmm(False, self.graph.val, self._linear_relu_z1(c.lin.weight, idx, out), self.p2, c.bias, 0.0, plan=plan,
+                           host=self._tail_host(1))
             elif self._mode == 'gin':
                 lin = c.nn
                 if lin.out_features > lin.in_features:
@@ -1045,7 +1077,8 @@ class NodeembEngine:
             else:
                 dt2, plan = (self._dt2_keep if chain else torch.empty(self.n, self.o, dtype=torch.float32, device=self.x.device)), None
             if self._mode == 'gcn':
-                self._spmm(True, g.val_t, self.dz2, dt2, None, 0.0, plan=plan)
+                # (_tail_hosted: this launch carries W_D2's job of the tail and the loss finalize - the last launch of the step)
+                self._spmm(True, g.val_t, self.dz2, dt2, None, 0.0, plan=plan, host=self._tail_host(2))
                 w2 = c.lin.weight
             else:
                 self._spmm(True, None, self.dz2, dt2, None, 1.0 + c.eps, plan=plan)
@@ -1074,12 +1107,41 @@ class NodeembEngine:
         # ReLU backward is applied in the GEMM epilogue so dh can outlive this iteration's z1)
         ops.rows_gemm(dt2, self.idx1, w2, trans_w=False, out=self.dh, gate_bits=self.z1_pos)
 
-    def _spmm(self, transposed, val, x, y, bias, self_coef, x_self=None, plan=None):
+    def _spmm(self, transposed, val, x, y, bias, self_coef, x_self=None, plan=None, host=None):
         g = self.graph
         if transposed:
-            ops._spmm_raw(g.rowptr_t, g.col_t, val, x, bias, self_coef, self.n, plan or g.plan_t, out=y, x_self=x_self)
+            ops._spmm_raw(g.rowptr_t, g.col_t, val, x, bias, self_coef, self.n, plan or g.plan_t, out=y, x_self=x_self, host=host)
         else:
-            ops._spmm_raw(g.rowptr, g.col, val, x, bias, self_coef, self.n, plan or g.plan, out=y, x_self=x_self)
+            ops._spmm_raw(g.rowptr, g.col, val, x, bias, self_coef, self.n, plan or g.plan, out=y, x_self=x_self, host=host)
+
+    def step_stages(self):
+        """The launches of one step of the chained GCN step folded in both layers, in order, by the stage labels of
+        tools/rocpd_stage_table.py; None for every other step (DESIGN.md lists theirs).  Derived from the forms alone."""
+        if not (self._fold1 and self._fold2 and self._chain1 and self._tail and not self._rows_only):
+            return None
+        stages = ['spmm1'] + ([] if self._chain_expl else ['pre1_rest']) + ['del1_loss_wgrad1', 't2', 'spmm2', 'del2_loss_bwd', 'spmm2_t']
+        return stages + ([] if self._tail_hosted else ['tail'])
+
+    def _loss_partials(self):
+        """(partials of layer 1, their count, partials of layer 2, their count) as the loss finalize reads them."""
+        p1, n1 = ((self._lp1, self._lp1_blocks + (self.t1.outside_blocks() if self._out1 else 0)) if self._fuse_loss1
+                  else (self.t1.partials, self.t1.n_partial_blocks()))
+        p2, n2 = ((self._lp2, self._lp2_blocks + (self.t2.outside_blocks() if self._out2 else 0)) if self._fuse_l2
+                  else (self.t2.partials, self.t2.n_partial_blocks()))
+        return p1, n1, p2, n2
+
+    def _tail_host(self, job):
+        """The job arguments of gd_spmm_csr_onepass_wide_hosted_f32 (_tail_hosted): job 1 = W_D1's column job (Adam, the next
+        step's W1^T W_D1 / b1 W_D1), job 2 = W_D2's reduction + Adam and the loss finalize; None where the tail has its own launch."""
+        if not self._tail_hosted:
+            return None
+        a1, a2 = self.adam1, self.adam2
+        p1, n1, p2, n2 = self._loss_partials()
+        return (ptr(self.ws1), ptr(self._cs1), self._lp1_blocks if job == 1 else 0, self.h, ptr(self._w1), ptr(self._w1t), ptr(self._b1),
+                ptr(self.g1), ptr(a1.param), ptr(a1.m), ptr(a1.v), ptr(self._wf), ptr(self._bf),
+                ptr(self.ws2), self._lp2_blocks if job == 2 else 0, self.o, self._tail_acc[1], ptr(self.g2), ptr(a2.param), ptr(a2.m),
+                ptr(a2.v), a1.lr, a1.betas[0], a1.betas[1], a1.eps,
+                ptr(p1), n1, ptr(p2), n2, ptr(self.hist), self.hist.shape[0], ptr(self.hist_pos), ptr(self.iter_ctr), ptr(self._arrive))
 
     def _wgrad(self, a_compact, g, g_idx, n_sel, out, accumulate, ws, adam=None, g_add=None, a_idx=None):
         """out (+)= a^T (g + g_add) over the selected rows; with `adam` the optimizer update of that Del
@@ -1199,11 +1261,10 @@ class NodeembEngine:
             if lt != 'only1' and not self._fuse_l2 and not self._tail:      # (else W_D2's step rode on a launch above or waits in the tail)
                 self.adam2.apply(self.g2)
             # ---- loss sums -> history ring, advance the iteration counter (Adam's step number)
-            p1, n1 = ((self._lp1, self._lp1_blocks + (self.t1.outside_blocks() if self._out1 else 0)) if self._fuse_loss1
-                      else (self.t1.partials, self.t1.n_partial_blocks()))
-            p2, n2 = ((self._lp2, self._lp2_blocks + (self.t2.outside_blocks() if self._out2 else 0)) if self._fuse_l2
-                      else (self.t2.partials, self.t2.n_partial_blocks()))
-            if self._tail:
+            p1, n1, p2, n2 = self._loss_partials()
+            if self._tail_hosted:
+                pass                                             # (both jobs and the finalize rode on the layer-2 aggregations)
+            elif self._tail:
                 a1, a2 = self.adam1, self.adam2
                 lib_ = _lib.lib()
                 nw1 = self._lp1_blocks if self._fuse_del1 else lib_.gd_rows_gemm_wgrad_blocks(self.s1)      # partial matrices of W_D1

@@ -33,10 +33,28 @@ def _f32_rows(t):
 
 
 
-def _spmm_raw(rowptr, col, val, x, bias, self_coef, n_rows, plan=None, out=None, x_self=None, wide=True):
+def spmm_wide_form(d, x_rows, ld_x, ld_y, env=None):
+    """Does _spmm_raw run a planned aggregation of these shapes on the wide 64-float form (gd_spmm_csr_onepass_wide_f32)?
+    d: row width, x_rows: the larger row count of x and y, ld_x / ld_y: their pitches in floats (multiples of 4).  Pure."""
+    env = os.environ if env is None else env
+    return bool(d == 64 and ld_x % 4 == 0 and x_rows < (1 << 24) and ld_x * 4 < (1 << 24) and ld_y * 4 < (1 << 24)
+                and x_rows * ld_x * 4 < (1 << 32) and x_rows * ld_y * 4 < (1 << 32) and env.get('GD_SPMM_TWO_LAUNCH') != '1'
+                and env.get('GD_SPMM_MULTIROW') != '0' and not env.get('GD_SPMM_D64_FORM'))
+
+
+def _no_host(host):
+    """No form of the aggregation but the wide one carries jobs of the step tail: a caller that passed them gets an error, not a
+    launch without them."""
+    if host is not None:
+        raise _lib.GnnDeleteHipError('the step tail can only ride on the wide 64-float aggregation (gd_spmm_csr_onepass_wide_hosted_f32)')
+
+
+def _spmm_raw(rowptr, col, val, x, bias, self_coef, n_rows, plan=None, out=None, x_self=None, wide=True, host=None):
     """y = self_coef * x_self + A x + bias (x_self = x unless given; same row pitch).  With a SplitPlan
     (and a float4-able width) the load-balanced kernel is used, otherwise the one-wave-per-row kernel.
-    wide=False keeps 64-float rows on the item kernel of gd_spmm_csr_onepass_f32 (a caller that needs its summation order)."""
+    wide=False keeps 64-float rows on the item kernel of gd_spmm_csr_onepass_f32 (a caller that needs its summation order).
+    host: the 34 job arguments of gd_spmm_csr_onepass_wide_hosted_f32 (between xcd_bounds and the stream) - the launch carries
+    jobs of the step tail; only the wide form takes them, any other form raises."""
     d = x.shape[1]
     if x_self is not None:
         assert plan is not None and x_self.stride(0) == x.stride(0) and x_self.shape[1] == d
@@ -45,23 +63,25 @@ def _spmm_raw(rowptr, col, val, x, bias, self_coef, n_rows, plan=None, out=None,
             and os.environ.get('GD_SPMM_TWO_LAUNCH') != '1'):
         # hub rows summed by the four waves of a block inside the same launch (no scratch rows, no fix-up kernel)
         x_rows = max(int(x.shape[0]), int(y.shape[0]))
-        if (wide and d == 64 and x_rows < (1 << 24) and x.stride(0) * 4 < (1 << 24) and y.stride(0) * 4 < (1 << 24)
-                and x_rows * x.stride(0) * 4 < (1 << 32) and x_rows * y.stride(0) * 4 < (1 << 32)
-                and os.environ.get('GD_SPMM_MULTIROW') != '0' and not os.environ.get('GD_SPMM_D64_FORM')):
+        if wide and spmm_wide_form(d, x_rows, x.stride(0), y.stride(0)):
             # 64-float rows: up to 16 light rows per item, summed by the fp32 matrix instruction (gd_spmm_csr_onepass_wide_f32);
             # GD_SPMM_D64_FORM=pairs (any lab form) keeps the two-row items of the vector kernel (A/B), GD_SPMM_MULTIROW=0 its one-row items
             items, n_items, bounds, tags = plan.onepass_wide(d)
-            check(_lib.lib().gd_spmm_csr_onepass_wide_f32(ptr(items), n_items, ptr(_wide_col(plan, col, tags)), ptr(val), ptr(x), x.stride(0),
-                                                          ptr(y), y.stride(0), ptr(bias), float(self_coef), ptr(x_self), d,
-                                                          int(col.shape[0]), x_rows, ptr(bounds), stream_ptr(x.device)),
-                  'gd_spmm_csr_onepass_wide_f32')
+            args = (ptr(items), n_items, ptr(_wide_col(plan, col, tags)), ptr(val), ptr(x), x.stride(0), ptr(y), y.stride(0), ptr(bias),
+                    float(self_coef), ptr(x_self), d, int(col.shape[0]), x_rows, ptr(bounds))
+            if host is not None:
+                check(_lib.lib().gd_spmm_csr_onepass_wide_hosted_f32(*args, *host, stream_ptr(x.device)), 'gd_spmm_csr_onepass_wide_hosted_f32')
+                return y
+            check(_lib.lib().gd_spmm_csr_onepass_wide_f32(*args, stream_ptr(x.device)), 'gd_spmm_csr_onepass_wide_f32')
             return y
+        _no_host(host)
         items, n_items, bounds = plan.onepass(d)
         check(_lib.lib().gd_spmm_csr_onepass_f32(ptr(items), n_items, ptr(col), ptr(val), ptr(x), x.stride(0), ptr(y),
                                                  y.stride(0), ptr(bias), float(self_coef), ptr(x_self), d, int(col.shape[0]),
                                                  max(int(x.shape[0]), int(y.shape[0])), ptr(bounds), stream_ptr(x.device)),
               'gd_spmm_csr_onepass_f32')
         return y
+    _no_host(host)
     if plan is not None and d % 4 == 0 and d <= 1024 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0:
         scratch = plan.scratch(d, x.device)
         check(_lib.lib().gd_spmm_csr_balanced_f32(ptr(plan.items), plan.n_items, ptr(plan.split), plan.n_split,

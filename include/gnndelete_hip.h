@@ -752,6 +752,31 @@ int gd_step_tail_fold1_f32(const float* partials1_t, const float* colsum1, int32
                            float* dw2, float* param2, float* exp_avg2, float* exp_avg_sq2, double lr, double beta1, double beta2,
                            double eps, const float* loss_partials1, int32_t n1, const float* loss_partials2, int32_t n2,
                            float* hist, int32_t capacity, int32_t* pos, int32_t* iter, int32_t* arrive, void* stream);
+/* gd_spmm_csr_onepass_wide_f32 (its first 15 arguments, the same y bit for bit) whose launch also carries jobs of
+ * gd_step_tail_fold1_f32 as extra blocks in front of the sweep (entry added: the ABI version stays).  The aggregation is
+ * fabric-bound with eight small blocks per compute unit; a few hundred short blocks that start first disappear in it, and a step
+ * that rides its tail on two such launches makes one launch less.
+ *   job 1 (n_part1 > 0; d1 must be 128): weight 1 of gd_step_tail_fold1_f32 - dw1, Adam on param1, w_fold, bias_fold - with the
+ *          step number *iter + 1.  w1_t: the transposed copy of w1 ([in][out], constant like w1).  *iter is only read.
+ *   job 2 (n_part2 > 0; d2 a multiple of 4, at most 128): weight 2 of that entry with the step number *iter + 1, then the loss
+ *          finalize: history row at *pos, *pos advanced modulo capacity, *iter advanced, *arrive back at 0 (it must be 0 at the
+ *          launch).  No block waits for another: in a launch with job 2 every job block - of job 1 too, where the launch carries
+ *          both - reads *iter first and adds 1 to *arrive when its work is done, and the finalize is run by whichever block's add
+ *          comes last, so the counter advances only after every job block of the launch has read it.
+ * n_part1 = 0 or n_part2 = 0 leaves that job out (its pointers are not read; job 1 alone touches neither *arrive nor the history);
+ * both 0: GD_E_DIM.  Every output is bit-equal to gd_step_tail_fold1_f32's on the same inputs.  A launch with both jobs steps both
+ * weights with the same step number.  A step that puts job 1 on one launch and job 2 on a LATER one of the same stream gets the
+ * tail's result: job 1's launch has ended before job 2's launch advances *iter.  Nothing depends on the order in which the blocks
+ * of a launch are dispatched.
+ * n_items must be > 0 (GD_E_DIM: there is no launch to ride on). */
+int gd_spmm_csr_onepass_wide_hosted_f32(
+    const int32_t* items, int32_t n_items, const int32_t* col_tagged, const float* val, const float* x, int64_t ldx, float* y, int64_t ldy,
+    const float* bias, float self_coef, const float* x_self, int32_t d, int32_t nnz, int32_t x_rows, const int32_t* xcd_bounds,
+    const float* partials1_t, const float* colsum1, int32_t n_part1, int32_t d1, const float* w1, const float* w1_t, const float* b1,
+    float* dw1, float* param1, float* exp_avg1, float* exp_avg_sq1, float* w_fold, float* bias_fold, const float* partials2,
+    int32_t n_part2, int32_t d2, int32_t accumulate2, float* dw2, float* param2, float* exp_avg2, float* exp_avg_sq2, double lr,
+    double beta1, double beta2, double eps, const float* loss_partials1, int32_t n1, const float* loss_partials2, int32_t n2, float* hist,
+    int32_t capacity, int32_t* pos, int32_t* iter, int32_t* arrive, void* stream);
 
 /* ---------------------------------------------------------------- losses --------------- */
 

@@ -7,7 +7,10 @@ guide: FETCH_SIZE counts 32 B per request where the 16-B/lane gathers move 64 ->
   python tools/rocpd_stage_table.py kt.db [--fetch f.db] [--write w.db] [--marker loss_finalize] [--out stages.json]
         [--stages name,name,...]   (labels by position; default = the GCN both_layerwise step with GD_LAYER1_FOLD=0; 'fold1' = the same
                                     step with conv1's weight folded into W_D1 and GD_EXPLICIT_CHAIN=0; 'chain' = the folded step of
-                                    seven launches, conv1's explicit rows formed inside t2; 'auto' = k00, k01, ... for any step)
+                                    seven launches, conv1's explicit rows formed inside t2; 'hosted' = the six launches of that step
+                                    with the tail's jobs inside spmm2 / spmm2_t - its last launch has the name of an earlier one, so
+                                    it is delimited by --marker del_loss --after 1 (the defaults with this list); 'auto' = k00, k01, ... for any step)
+        [--after K]                (the step ends K launches behind the marker kernel; default 0 = the marker is the last launch)
 """
 import argparse
 import json
@@ -18,6 +21,8 @@ GCN_STEP_FOLD1 = ['spmm1', 'pre1_rest', 'del1_loss_wgrad1', 't2', 'spmm2', 'del2
 #   spmm1 aggregates x itself, pre1_rest = a W1^T + b1 on the rows outside the Del-1 mask; pass --stages with this list)
 GCN_STEP_CHAIN = ['spmm1', 'del1_loss_wgrad1', 't2', 'spmm2', 'del2_loss_bwd', 'spmm2_t', 'tail']   # (seven launches: the folded step with
 #   pre1_rest formed inside t2, gd_rows_gemm_select_chain_f32; --stages chain)
+GCN_STEP_HOSTED = ['spmm1', 'del1_loss_wgrad1', 't2', 'spmm2', 'del2_loss_bwd', 'spmm2_t']   # (six launches: W_D1's job of the tail inside
+#   spmm2, W_D2's job and the loss finalize inside spmm2_t, gd_spmm_csr_onepass_wide_hosted_f32; --stages hosted --marker del_loss --after 1)
 GCN_STEP_R05A = ['xw1', 'spmm1', 'del1_loss_wgrad1', 't2', 'spmm2', 'del2_loss_bwd', 'spmm2_t', 'dh', 'tail']   # (GD_DEL1_CHAIN=0)
 GCN_STEP_R04 = ['xw1', 'spmm1', 'del1', 'wgrad1', 't2', 'spmm2', 'del2_loss_bwd', 'spmm2_t', 'dh', 'tail']     # (GD_DEL1_FUSED=0: two launches)
 
@@ -40,15 +45,19 @@ def main():
     ap.add_argument('db')
     ap.add_argument('--fetch')
     ap.add_argument('--write')
-    ap.add_argument('--marker', default='step_tail')
+    ap.add_argument('--marker', help="kernel whose launch delimits a step (default: step_tail; with --stages hosted: del_loss, one launch before the end)")
     ap.add_argument('--stages', default=','.join(GCN_STEP))
+    ap.add_argument('--after', type=int, help='launches between the marker kernel and the end of the step (default 0; 1 with --stages hosted)')
     ap.add_argument('--skip', type=int, default=8, help='leading steps left out (warm-up, eager capture passes)')
     ap.add_argument('--out')
     a = ap.parse_args()
+    if a.marker is None:                # (the six-launch step has no tail kernel, and its last launch has the name of its fourth)
+        a.marker, a.after = ('del_loss', 1 if a.after is None else a.after) if a.stages == 'hosted' else ('step_tail', a.after)
+    a.after = a.after or 0
     rows = kernels(a.db)
-    marks = [i for i, r in enumerate(rows) if a.marker in r[0]]
+    marks = [i + a.after for i, r in enumerate(rows) if a.marker in r[0] and i + a.after < len(rows)]
     steps = [rows[marks[j] + 1: marks[j + 1] + 1] for j in range(len(marks) - 1)]
-    labels = {'fold1': GCN_STEP_FOLD1, 'chain': GCN_STEP_CHAIN}.get(a.stages) or a.stages.split(',')
+    labels = {'fold1': GCN_STEP_FOLD1, 'chain': GCN_STEP_CHAIN, 'hosted': GCN_STEP_HOSTED}.get(a.stages) or a.stages.split(',')
     if a.stages == 'auto':              # any step: the most frequent kernel count between two markers, labels by position
         from collections import Counter
         k = Counter(len(s) for s in steps[a.skip:]).most_common(1)[0][0]
