@@ -889,6 +889,8 @@ extern "C" int gd_spmm_csr_balanced_f32(const int32_t* items, int32_t n_items, c
              "gd_spmm_csr_balanced_f32: unaligned pointer");
   GD_REQUIRE(x != y, GD_E_DIM, "gd_spmm_csr_balanced_f32: x and y must not alias");
   if (n_items == 0) return GD_OK;
+  // (the sweep clamps its index prefetch to nnz - 1: with items and no edge at all that is col[-1])
+  GD_REQUIRE(nnz > 0, GD_E_DIM, "gd_spmm_csr_balanced_f32: items over an index array without entries (nnz=%d)", nnz);
   hipStream_t s = (hipStream_t)stream;
   const int d4 = d / 4;
   const float* xs = x_self ? x_self : x;            // rows of the self / residual term (same pitch as x)
@@ -916,6 +918,7 @@ extern "C" int gd_spmm_csr_onepass_f32(const int32_t* items, int32_t n_items, co
              "gd_spmm_csr_onepass_f32: unaligned pointer");
   GD_REQUIRE(x != y, GD_E_DIM, "gd_spmm_csr_onepass_f32: x and y must not alias");
   if (n_items == 0) return GD_OK;
+  GD_REQUIRE(nnz > 0, GD_E_DIM, "gd_spmm_csr_onepass_f32: items over an index array without entries (nnz=%d)", nnz);
   const float* xs = x_self ? x_self : x;
   GD_REQUIRE(aligned16(xs) && xs != y, GD_E_ALIGN, "gd_spmm_csr_onepass_f32: bad x_self");
   return launch_persist(items, n_items, col, val, x, ldx, y, ldy, bias, self_coef, xs, nullptr, d, nnz, x_rows,
@@ -937,6 +940,7 @@ static int launch_wide(const char* name, const int32_t* items, int32_t n_items, 
              "%s: x and y must be smaller than 4 GiB with row ids and pitches below 2^24", name);
   GD_REQUIRE(!host || n_items > 0, GD_E_DIM, "%s: the tail's jobs need a launch to ride on (n_items = 0)", name);
   if (n_items == 0) return GD_OK;
+  GD_REQUIRE(nnz > 0, GD_E_DIM, "%s: items over an index array without entries (nnz=%d)", name, nnz);
   const float* xs = x_self ? x_self : x;
   GD_REQUIRE(aligned16(xs) && xs != y, GD_E_ALIGN, "%s: bad x_self", name);
   const char* e = getenv("GD_SPMM_GRID_CAP");               // tuning knob (blocks)
@@ -1020,6 +1024,7 @@ extern "C" int gd_spmm_csr_onepass_aux_f32(const int32_t* items, int32_t n_items
                  (int64_t)x_rows * ldx * 4 < (1ll << 32) && (int64_t)x_rows * ldy * 4 < (1ll << 32), GD_E_DIM,
              "gd_spmm_csr_onepass_aux_f32: x and y must be smaller than 4 GiB with row ids and pitches below 2^24");
   if (n_items == 0) return GD_OK;
+  GD_REQUIRE(nnz > 0, GD_E_DIM, "gd_spmm_csr_onepass_aux_f32: items over an index array without entries (nnz=%d)", nnz);
   int nblk = (n_items + 3) / 4;
   if (nblk > 8192) nblk = 8192;
   nblk = (nblk + 7) / 8 * 8;

@@ -59,6 +59,21 @@ def _spmm_raw(rowptr, col, val, x, bias, self_coef, n_rows, plan=None, out=None,
     if x_self is not None:
         assert plan is not None and x_self.stride(0) == x.stride(0) and x_self.shape[1] == d
     y = out if out is not None else torch.empty(n_rows, d, dtype=torch.float32, device=x.device)
+    if int(col.shape[0]) == 0:
+        # an edgeless graph (GINConv / SAGEConv on an edge list without edges reach this): there is no aggregation to launch - the
+        # item entries refuse items over an empty index array (GD_E_DIM, include/gnndelete_hip.h) - and y = self_coef x_self + bias
+        # on the plan's rows is all that is left of the operation
+        _no_host(host)
+        xs = x if x_self is None else x_self
+        r = xs[:n_rows] * float(self_coef) if self_coef != 0.0 else torch.zeros(n_rows, d, dtype=torch.float32, device=x.device)
+        if bias is not None:
+            r = r + bias
+        outside = plan.rows_outside() if plan is not None else None
+        if outside is None:
+            y[:n_rows].copy_(r)
+        else:
+            y[:n_rows][~outside] = r[~outside]
+        return y
     if (plan is not None and d % 4 == 0 and d <= 1024 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
             and os.environ.get('GD_SPMM_TWO_LAUNCH') != '1'):
         # hub rows summed by the four waves of a block inside the same launch (no scratch rows, no fix-up kernel)

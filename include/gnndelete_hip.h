@@ -133,7 +133,10 @@ int gd_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val,
  * item covers its whole row (y written directly), else the index of a d-float partial in
  * `scratch`.  split[4*i..] = {row, first_slot, n_slots, 0} lists the rows cut into several
  * items; their partials are added in slot order by a second kernel (no atomics: deterministic).
- * nnz = length of col/val (index loads are clamped to it instead of being predicated).
+ * nnz = length of col/val (index loads are clamped to it instead of being predicated).  The clamp is to nnz - 1, so a
+ * table of items over an index array WITHOUT entries has nothing to clamp to: n_items > 0 with nnz <= 0 is GD_E_DIM (no
+ * launch) in this entry, in gd_spmm_csr_onepass_f32, gd_spmm_csr_onepass_wide_f32 (and its hosted form) and
+ * gd_spmm_csr_onepass_aux_f32.  An edgeless aggregation is the caller's: y = self_coef * x_self + bias.
  * x_self (optional, same pitch ldx): the matrix the self_coef term is read from, y[i] += self_coef *
  * x_self[i,:]; NULL = x itself (GIN's (1+eps) x_i).  With another matrix (or other columns of the
  * same buffer) and self_coef = 1 it is SAGEConv's root path, out = mean_j(x_j W_l) + b + x_i W_r.
