@@ -661,6 +661,229 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   spmm_wide_body(items, n_items, xcd_bounds, colt, val, x, ldx, y, ldy, bias, self_coef, xs, nnz, blockIdx.x, gridDim.x);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The wide form at rows of exactly 128 floats (gd_spmm_csr_onepass_wide128_f32): spmm_wide_body with two 64-float halves per row.
+// Items, row tags and the tagged index array do not depend on the width and are the 64-float form's.  The lane layout is kept
+// (g = lane >> 4 on edge slot 4t + g, li = lane & 15): a trip loads TWO float4 per lane from the same source row, features 4 li ..
+// and 64 + 4 li .. (one address, + 256 B), and issues EIGHT matrix instructions that share the one A value, (tag == li) ? weight : 0;
+// eight accumulators start from the bias, and the epilogue stores two float4 per row and lane, with the self term as at d = 64.  A
+// GROUP member (slot -2) runs the vector path of spmm_persist_body<32, 1, 4> - two lane groups of 32 lanes, two edges per trip - trip
+// for trip: hub rows keep the bits of gd_spmm_csr_onepass_f32 at d = 128.  The NON-FINITE CAVEAT of the 64-float form holds here too.
+// A sibling of spmm_wide_body, not an instantiation of one template: with the body templated on the halves the compiler allocated the
+// 64-float kernels' registers differently (4366 instead of 4519 instructions in spmm_wide_kernel), and those two launches are
+// measured and merged as they are.  UM = trips in flight on the matrix path.
+// Resources (gfx950, clang of ROCm 7.2): UM = 2 at 7 waves per SIMD (what the launch runs): 68 VGPRs, 56 SGPRs, no scratch, 2560 B
+// of LDS per block (at 8 waves it spills 8 bytes per lane: not built); UM = 4 at 5 waves per SIMD (GD_SPMM_WIDE128_TRIPS=4): 93 VGPRs,
+// 57 SGPRs, no scratch, 2560 B.  Bench step, ms: 0.45045 with two trips, 0.45235 / 0.45150 with four (profiles/spmm_wide128_ab.txt).
+template <int UM>
+__device__ __forceinline__ void spmm_wide128_body(
+    const int4* __restrict__ items, int32_t n_items, const int32_t* __restrict__ xcd_bounds, const int32_t* __restrict__ colt,
+    const float* __restrict__ val, const float* __restrict__ x, int64_t ldx, float* __restrict__ y, int64_t ldy,
+    const float* __restrict__ bias, float self_coef, const float* __restrict__ xs, int32_t nnz, uint32_t bid, uint32_t nblk) {
+  constexpr int kXcd = 8, U = 4, H = 2;                             // H: 64-float halves of a row
+  constexpr int kSrcMask = (1 << 24) - 1;
+  constexpr int LH = 16 * H, GSH = 1;                               // hub path: lanes per row, log2 of its lane groups
+  const int lane = threadIdx.x & 63;
+  const int g = lane >> 4, li = lane & 15;
+  const int xcd = bid % kXcd;
+  const int stride = (nblk / kXcd) * 4;                             // waves per XCD
+  const int wx = (bid / kXcd) * 4 + (threadIdx.x >> 6);
+  const int i0 = xcd_bounds[xcd], i1 = xcd_bounds[xcd + 1];
+  // (the barrier invariant of the group path, checked where it costs the sweep no register: spmm_persist_body)
+  if ((i0 | i1) & 3) __builtin_trap();
+  const uint32_t lo = 16u * (uint32_t)li;
+  const uint32_t pitch_b = (uint32_t)ldx * 4u, pitch_y = (uint32_t)ldy * 4u;
+  const char* xb = reinterpret_cast<const char*>(x);
+
+  // (the wave's item index is wave-uniform: said so to the compiler, the descriptors are scalar loads into SGPRs - no lane-0
+  //  fetch, no vector registers held for them)
+  int i = __builtin_amdgcn_readfirstlane(i0 + wx);
+  if (i >= i1) return;
+  // descriptor two visits ahead, (index, weight) one visit ahead, as in spmm_persist_body
+  int4 d0 = items[i], d1 = items[min(i + stride, i1 - 1)];          // {row, start, end, slot}
+  int kk = min(d0.y + lane, nnz - 1);
+  int c = colt[kk];
+  float w = val ? val[kk] : 1.0f;
+  __shared__ float4 grp_red[4][LH];
+  // the bias (zeros without one) waits in LDS: an item starts its accumulators with one ds_read, no register or address is held
+  // for it across the sweep
+  __shared__ float4 bias_s[LH];
+  if (threadIdx.x < LH) bias_s[threadIdx.x] = bias ? reinterpret_cast<const float4*>(bias)[threadIdx.x] : f4_zero();
+  __syncthreads();
+  for (; i < i1; i += stride) {
+    const int row = d0.x, slot = d0.w;
+    const int c_now = c;
+    const float w_now = w;
+    const int4 d2 = items[min(i + 2 * stride, i1 - 1)];
+    kk = min(d1.y + lane, nnz - 1);
+    c = colt[kk];
+    w = val ? val[kk] : 1.0f;
+    if (slot != -2) {
+      // ---- up to 16 light rows on the matrix pipe
+      const int nr = -slot - 15;                         // rows of the item (<= 0: padding)
+      const int cnt = d0.z - d0.y;
+      const float w_cur = lane < cnt ? w_now : 0.f;
+      const int trips = (cnt + 3) >> 2;
+      // (padding slots of the last trip re-read the item's last neighbour and take weight 0 from lane `cnt`)
+      const int last4 = 4 * cnt - 4, end4 = 4 * cnt;
+      f32x4_t a[H][4];
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        const float4 bv = bias_s[16 * h + li];
+        a[h][0] = f32x4_t{bv.x, bv.x, bv.x, bv.x};
+        a[h][1] = f32x4_t{bv.y, bv.y, bv.y, bv.y};
+        a[h][2] = f32x4_t{bv.z, bv.z, bv.z, bv.z};
+        a[h][3] = f32x4_t{bv.w, bv.w, bv.w, bv.w};
+      }
+      auto fetch = [&](int t, float4(&xv)[H], float& av) {
+        const int j4 = 16 * t + 4 * g;
+        const int cs = __builtin_amdgcn_ds_bpermute(min(j4, last4), c_now);
+        const float wj = __int_as_float(__builtin_amdgcn_ds_bpermute(min(j4, end4), __float_as_int(w_cur)));
+        av = ((uint32_t)cs >> 24) == (uint32_t)li ? wj : 0.f;
+        const uint32_t ro = __umul24((uint32_t)(cs & kSrcMask), pitch_b);
+#pragma unroll
+        for (int h = 0; h < H; ++h) xv[h] = *reinterpret_cast<const float4*>(xb + (ro + lo) + 256 * h);
+      };
+      auto mma = [&](float av, const float4(&xv)[H]) {
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+          a[h][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xv[h].x, a[h][0], 0, 0, 0);
+          a[h][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xv[h].y, a[h][1], 0, 0, 0);
+          a[h][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xv[h].z, a[h][2], 0, 0, 0);
+          a[h][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xv[h].w, a[h][3], 0, 0, 0);
+        }
+      };
+      int t0 = 0;
+      for (; t0 + UM <= trips; t0 += UM) {
+        float4 xv[UM][H];
+        float av[UM];
+#pragma unroll
+        for (int u = 0; u < UM; ++u) fetch(t0 + u, xv[u], av[u]);
+        __builtin_amdgcn_sched_barrier(0);               // all the loads in flight before the first matrix instruction waits
+#pragma unroll
+        for (int u = 0; u < UM; ++u) mma(av[u], xv[u]);
+      }
+      // the last one to three trips, each count in a block of its own (a value defined and used under `u < rem` would stay
+      // allocated around the whole sweep)
+      const int rem = trips - t0;
+      if (rem == 1) {
+        float4 xv[1][H];
+        float av;
+        fetch(t0, xv[0], av);
+        mma(av, xv[0]);
+      } else if (UM > 2 && rem == 2) {
+        float4 xv[2][H];
+        float av[2];
+        fetch(t0, xv[0], av[0]);
+        fetch(t0 + 1, xv[1], av[1]);
+        mma(av[0], xv[0]);
+        mma(av[1], xv[1]);
+      } else if (UM > 2 && rem == 3) {
+        float4 xv[3][H];
+        float av[3];
+        fetch(t0, xv[0], av[0]);
+        fetch(t0 + 1, xv[1], av[1]);
+        fetch(t0 + 2, xv[2], av[2]);
+        mma(av[0], xv[0]);
+        mma(av[1], xv[1]);
+        mma(av[2], xv[2]);
+      }
+      // lane (n = li, q = g) holds rows row + 4q + j, features 4n .. 4n + 3 of every half; rows past the item's are not stored
+      const uint32_t r0 = (uint32_t)(row + 4 * g);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (4 * g + j < nr) {
+#pragma unroll
+          for (int h = 0; h < H; ++h) {
+            float4 o = make_float4(a[h][0][j], a[h][1][j], a[h][2][j], a[h][3][j]);
+            if (self_coef != 0.0f)
+              o = f4_fma(self_coef, *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(xs) + (__umul24(r0 + j, pitch_b) + lo) + 256 * h), o);
+            *reinterpret_cast<float4*>(reinterpret_cast<char*>(y) + (__umul24(r0 + j, pitch_y) + lo) + 256 * h) = o;
+          }
+        }
+      }
+    } else {
+      // ---- GROUP member of a hub row: the vector path of spmm_persist_body<32, 1, 4>, trip for trip (block-uniform branch: the
+      //      planner aligns the quadruples and the XCD ranges to 4)
+      const int gh = lane >> (6 - GSH), lh = lane & (LH - 1);
+      const uint32_t loh = 16u * (uint32_t)lh;
+      int base = d0.y;
+      int c_cur = c_now;
+      float w_raw = w_now;
+      float4 acc = f4_zero();
+      for (;;) {
+        const int cnt = min(kWave, d0.z - base);
+        const float w_cur = lane < cnt ? w_raw : 0.f;
+        const int trips = (cnt + (1 << GSH) - 1) >> GSH;
+        const int last4 = 4 * cnt - 4, end4 = 4 * cnt;
+        auto fetch = [&](int t, float4& xv, float& wj) {
+          const int j4 = (4 << GSH) * t + 4 * gh;
+          const int cs = __builtin_amdgcn_ds_bpermute(min(j4, last4), c_cur);
+          wj = __int_as_float(__builtin_amdgcn_ds_bpermute(min(j4, end4), __float_as_int(w_cur)));
+          const uint32_t ro = __umul24((uint32_t)(cs & kSrcMask), pitch_b);
+          xv = *reinterpret_cast<const float4*>(xb + (ro + loh));
+        };
+        int t0 = 0;
+        for (; t0 + U <= trips; t0 += U) {
+          float4 xv[U];
+          float wj[U];
+#pragma unroll
+          for (int u = 0; u < U; ++u) fetch(t0 + u, xv[u], wj[u]);
+#pragma unroll
+          for (int u = 0; u < U; ++u) acc = f4_fma(wj[u], xv[u], acc);
+        }
+        const int rem = trips - t0;
+        if (rem == 1) {
+          float4 xv;
+          float wj;
+          fetch(t0, xv, wj);
+          acc = f4_fma(wj, xv, acc);
+        } else if (rem == 2) {
+          float4 xv[2];
+          float wj[2];
+          fetch(t0, xv[0], wj[0]);
+          fetch(t0 + 1, xv[1], wj[1]);
+          acc = f4_fma(wj[1], xv[1], f4_fma(wj[0], xv[0], acc));
+        } else if (rem == 3) {
+          float4 xv[3];
+          float wj[3];
+          fetch(t0, xv[0], wj[0]);
+          fetch(t0 + 1, xv[1], wj[1]);
+          fetch(t0 + 2, xv[2], wj[2]);
+          acc = f4_fma(wj[2], xv[2], f4_fma(wj[1], xv[1], f4_fma(wj[0], xv[0], acc)));
+        }
+        base += kWave;
+        if (base >= d0.z) break;
+        const int k2 = min(base + lane, nnz - 1);
+        c_cur = colt[k2];
+        w_raw = val ? val[k2] : 1.0f;
+      }
+      acc = f4_group_sum<LH>(acc);
+      const int wave = threadIdx.x >> 6;
+      if (gh == 0) grp_red[wave][lh] = acc;
+      __syncthreads();
+      if (wave == 0 && gh == 0) {
+        float4 o = f4_add(f4_add(f4_add(grp_red[0][lh], grp_red[1][lh]), grp_red[2][lh]), grp_red[3][lh]);
+        if (self_coef != 0.0f)
+          o = f4_fma(self_coef, *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(xs) + (__umul24((uint32_t)row, pitch_b) + loh)), o);
+        if (bias) o = f4_add(o, bias_s[lh]);
+        *reinterpret_cast<float4*>(reinterpret_cast<char*>(y) + (__umul24((uint32_t)row, pitch_y) + loh)) = o;
+      }
+      __syncthreads();
+    }
+    d0 = d1;
+    d1 = d2;
+  }
+}
+
+template <int UM, int WAVES>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void spmm_wide128_kernel(
+    const int4* __restrict__ items, int32_t n_items, const int32_t* __restrict__ xcd_bounds, const int32_t* __restrict__ colt,
+    const float* __restrict__ val, const float* __restrict__ x, int64_t ldx, float* __restrict__ y, int64_t ldy,
+    const float* __restrict__ bias, float self_coef, const float* __restrict__ xs, int32_t nnz) {
+  spmm_wide128_body<UM>(items, n_items, xcd_bounds, colt, val, x, ldx, y, ldy, bias, self_coef, xs, nnz, blockIdx.x, gridDim.x);
+}
+
 // gd_spmm_csr_onepass_wide_hosted_f32: the launch carries the step tail's jobs in front of the sweep.  The first host.nh blocks of
 // the grid (a multiple of 8, so that the sweep blocks' XCD residues and xcd_bounds ranges are the unhosted launch's) run
 // tail_host_block and return; every sweep block is block blockIdx.x - nh of gridDim.x - nh.  The sweep is fabric-bound with 8 small
@@ -929,10 +1152,10 @@ namespace gd {
 // the wide launch, with the tail's jobs in front of the sweep where `host` is given (n_items > 0 then)
 static int launch_wide(const char* name, const int32_t* items, int32_t n_items, const int32_t* col_tagged, const float* val, const float* x,
                        int64_t ldx, float* y, int64_t ldy, const float* bias, float self_coef, const float* x_self, int32_t d,
-                       int32_t nnz, int32_t x_rows, const int32_t* xcd_bounds, const TailHost* host, void* stream) {
+                       int32_t nnz, int32_t x_rows, const int32_t* xcd_bounds, const TailHost* host, void* stream, int32_t width = 64) {
   GD_REQUIRE(col_tagged && x && y && xcd_bounds && (items || n_items == 0), GD_E_NULL, "%s: null pointer", name);
-  GD_REQUIRE(n_items >= 0 && n_items % 4 == 0 && d == 64 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= d && ldy >= d, GD_E_DIM,
-             "%s: d must be 64 (got %d) with 16-byte row strides, n_items a multiple of 4", name, d);
+  GD_REQUIRE(n_items >= 0 && n_items % 4 == 0 && d == width && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= d && ldy >= d, GD_E_DIM,
+             "%s: d must be %d (got %d) with 16-byte row strides, n_items a multiple of 4", name, width, d);
   GD_REQUIRE(aligned16(x) && aligned16(y) && aligned16(items) && (!bias || aligned16(bias)), GD_E_ALIGN, "%s: unaligned pointer", name);
   GD_REQUIRE(x != y, GD_E_DIM, "%s: x and y must not alias", name);
   GD_REQUIRE(x_rows > 0 && x_rows < (1 << 24) && ldx * 4 < (1 << 24) && ldy * 4 < (1 << 24) &&
@@ -949,6 +1172,17 @@ static int launch_wide(const char* name, const int32_t* items, int32_t n_items, 
   int nblk = (n_items + 3) / 4;
   if (nblk > cap) nblk = cap;
   nblk = (nblk + 7) / 8 * 8;
+  if (width == 128) {
+    // two trips in flight at 7 waves per SIMD (measured best in the bench step); GD_SPMM_WIDE128_TRIPS=4 (lab): four at 5 waves
+    const char* t = getenv("GD_SPMM_WIDE128_TRIPS");
+    if (t && atoi(t) == 4)
+      hipLaunchKernelGGL((spmm_wide128_kernel<4, 5>), dim3(nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const int4*>(items), n_items,
+                         xcd_bounds, col_tagged, val, x, ldx, y, ldy, bias, self_coef, xs, nnz);
+    else
+      hipLaunchKernelGGL((spmm_wide128_kernel<2, 7>), dim3(nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const int4*>(items), n_items,
+                         xcd_bounds, col_tagged, val, x, ldx, y, ldy, bias, self_coef, xs, nnz);
+    return launched("spmm_wide128");
+  }
   if (host) {
     hipLaunchKernelGGL(spmm_wide_hosted_kernel, dim3(host->nh + nblk), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const int4*>(items), n_items, xcd_bounds, col_tagged, val, x, ldx, y, ldy, bias, self_coef, xs, nnz,
@@ -967,6 +1201,14 @@ extern "C" int gd_spmm_csr_onepass_wide_f32(const int32_t* items, int32_t n_item
                                             const int32_t* xcd_bounds, void* stream) {
   return gd::launch_wide("gd_spmm_csr_onepass_wide_f32", items, n_items, col_tagged, val, x, ldx, y, ldy, bias, self_coef, x_self, d, nnz,
                          x_rows, xcd_bounds, nullptr, stream);
+}
+
+extern "C" int gd_spmm_csr_onepass_wide128_f32(const int32_t* items, int32_t n_items, const int32_t* col_tagged, const float* val,
+                                               const float* x, int64_t ldx, float* y, int64_t ldy, const float* bias,
+                                               float self_coef, const float* x_self, int32_t d, int32_t nnz, int32_t x_rows,
+                                               const int32_t* xcd_bounds, void* stream) {
+  return gd::launch_wide("gd_spmm_csr_onepass_wide128_f32", items, n_items, col_tagged, val, x, ldx, y, ldy, bias, self_coef, x_self, d,
+                         nnz, x_rows, xcd_bounds, nullptr, stream, 128);
 }
 
 extern "C" int gd_spmm_csr_onepass_wide_hosted_f32(

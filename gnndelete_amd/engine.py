@@ -953,7 +953,7 @@ class NodeembEngine:
         elif self._mode == 'gcn' and self._fold1:
             # a = A^ x (the rows-only step: on the S2 rows; x is complete, so no transformed buffer and no closure condition here),
             # then conv1's output on the rows outside S1 alone
-            self._spmm(False, g.val, self.x, self._a1, None, 0.0, plan=self._plan2 if self._rows_only else None)
+            self._spmm(False, g.val, self.x, self._a1, None, 0.0, plan=self._plan2 if self._rows_only else None, wide128=True)
             if self._idx1c.numel() and not self._chain_expl:          # (_chain_expl: formed where conv2's Linear reads it)
                 ops.rows_gemm(self._a1, self._idx1c, self._w1, trans_w=True, const_w=True, bias=self._b1, out=self.pre1)
         elif self._mode == 'gcn':
@@ -1107,12 +1107,15 @@ class NodeembEngine:
         # ReLU backward is applied in the GEMM epilogue so dh can outlive this iteration's z1)
         ops.rows_gemm(dt2, self.idx1, w2, trans_w=False, out=self.dh, gate_bits=self.z1_pos)
 
-    def _spmm(self, transposed, val, x, y, bias, self_coef, x_self=None, plan=None, host=None):
+    def _spmm(self, transposed, val, x, y, bias, self_coef, x_self=None, plan=None, host=None, wide128=False):
+        """wide128: the wide form at 128-float rows - asked for by the GCN step folded in layer 1 alone: measured in the bench step
+        GraphSAGE's layer-1 aggregation gains with it and GIN's (a self row per target, fetched in the wide epilogue) loses
+        (profiles/spmm_wide128_ab.txt), so the other models keep the item kernel."""
         g = self.graph
         if transposed:
-            ops._spmm_raw(g.rowptr_t, g.col_t, val, x, bias, self_coef, self.n, plan or g.plan_t, out=y, x_self=x_self, host=host)
+            ops._spmm_raw(g.rowptr_t, g.col_t, val, x, bias, self_coef, self.n, plan or g.plan_t, out=y, x_self=x_self, host=host, wide128=wide128)
         else:
-            ops._spmm_raw(g.rowptr, g.col, val, x, bias, self_coef, self.n, plan or g.plan, out=y, x_self=x_self, host=host)
+            ops._spmm_raw(g.rowptr, g.col, val, x, bias, self_coef, self.n, plan or g.plan, out=y, x_self=x_self, host=host, wide128=wide128)
 
     def step_stages(self):
         """The launches of one step of the chained GCN step folded in both layers, in order, by the stage labels of

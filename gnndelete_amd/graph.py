@@ -22,6 +22,10 @@ WIDE_VISIT_COST = 48   # what a visit of that form costs its XCD beside its in-e
                        # the bench step: the two launches together 106.9 / 104.3 / 105.3 / 105.5 us, profiles/spmm_wide_ab.txt)
 
 
+WIDE128_VISIT_COST = 48   # ... and of the 128-float form (onepass_wide128): the 64-float form's value - the same items, so one item table
+                          # and one tagged index array serve both widths
+
+
 class SplitPlan:
     """Work items of the load-balanced SpMM (gd_spmm_csr_balanced_f32): every CSR row is cut
     into pieces of at most CHUNK in-edges so that hub rows are spread over many waves."""
@@ -350,6 +354,15 @@ class SplitPlan:
         hit = (items, total, torch.tensor(bounds, dtype=torch.int32, device=dev), tags)
         self._onepass[key] = hit
         return hit
+
+    def onepass_wide128(self, visit_cost=None):
+        """(items, n, bounds, tags) for gd_spmm_csr_onepass_wide128_f32.  Items and row tags do not depend on the width: these are
+        onepass_wide(64)'s, with the XCD ranges balanced at this form's own visit cost (WIDE128_VISIT_COST; a range limit decides
+        where the rows above 4 pieces and the padding of its range go, so another cost is another item table) and, whatever the
+        cost, the tags of the 64-float plan - one tagged index array per CSR."""
+        a = WIDE128_VISIT_COST if visit_cost is None else int(visit_cost)
+        items, n, bounds, _ = self.onepass_wide(64, visit_cost=a)
+        return items, n, bounds, self.onepass_wide(64)[3]
 
     def rows_outside(self):
         """bool [rows of the CSR]: True on the rows that are NOT in the plan, None for a plan over every row (built with the

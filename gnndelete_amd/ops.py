@@ -42,6 +42,16 @@ def spmm_wide_form(d, x_rows, ld_x, ld_y, env=None):
                 and env.get('GD_SPMM_MULTIROW') != '0' and not env.get('GD_SPMM_D64_FORM'))
 
 
+def spmm_wide128_form(d, x_rows, ld_x, ld_y, env=None):
+    """May _spmm_raw run a planned aggregation of these shapes on the wide 128-float form (gd_spmm_csr_onepass_wide128_f32)?  It
+    does where the caller asks for it (wide128=True: the GCN step folded in layer 1) or GD_SPMM_D128_FORM=wide does.  The conditions
+    of spmm_wide_form at d = 128; GD_SPMM_D128_FORM=items keeps the one-row items of the vector kernel everywhere (A/B).  Pure."""
+    env = os.environ if env is None else env
+    return bool(d == 128 and ld_x % 4 == 0 and x_rows < (1 << 24) and ld_x * 4 < (1 << 24) and ld_y * 4 < (1 << 24)
+                and x_rows * ld_x * 4 < (1 << 32) and x_rows * ld_y * 4 < (1 << 32) and env.get('GD_SPMM_TWO_LAUNCH') != '1'
+                and env.get('GD_SPMM_MULTIROW') != '0' and env.get('GD_SPMM_D128_FORM') != 'items')
+
+
 def _no_host(host):
     """No form of the aggregation but the wide one carries jobs of the step tail: a caller that passed them gets an error, not a
     launch without them."""
@@ -49,10 +59,12 @@ def _no_host(host):
         raise _lib.GnnDeleteHipError('the step tail can only ride on the wide 64-float aggregation (gd_spmm_csr_onepass_wide_hosted_f32)')
 
 
-def _spmm_raw(rowptr, col, val, x, bias, self_coef, n_rows, plan=None, out=None, x_self=None, wide=True, host=None):
+def _spmm_raw(rowptr, col, val, x, bias, self_coef, n_rows, plan=None, out=None, x_self=None, wide=True, host=None, wide128=False):
     """y = self_coef * x_self + A x + bias (x_self = x unless given; same row pitch).  With a SplitPlan
     (and a float4-able width) the load-balanced kernel is used, otherwise the one-wave-per-row kernel.
-    wide=False keeps 64-float rows on the item kernel of gd_spmm_csr_onepass_f32 (a caller that needs its summation order).
+    wide=False keeps 64- and 128-float rows on the item kernel of gd_spmm_csr_onepass_f32 (a caller that needs its summation order).
+    wide128=True asks for the wide form at 128-float rows (gd_spmm_csr_onepass_wide128_f32) where spmm_wide128_form holds - the GCN
+    step folded in layer 1 does; GD_SPMM_D128_FORM=wide asks for it at every planned 128-float aggregation, =items at none.
     host: the 34 job arguments of gd_spmm_csr_onepass_wide_hosted_f32 (between xcd_bounds and the stream) - the launch carries
     jobs of the step tail; only the wide form takes them, any other form raises."""
     d = x.shape[1]
@@ -90,6 +102,14 @@ def _spmm_raw(rowptr, col, val, x, bias, self_coef, n_rows, plan=None, out=None,
             check(_lib.lib().gd_spmm_csr_onepass_wide_f32(*args, stream_ptr(x.device)), 'gd_spmm_csr_onepass_wide_f32')
             return y
         _no_host(host)
+        if wide and (wide128 or os.environ.get('GD_SPMM_D128_FORM') == 'wide') and spmm_wide128_form(d, x_rows, x.stride(0), y.stride(0)):
+            # 128-float rows: the same items, two float4 per lane and trip, eight matrix instructions (gd_spmm_csr_onepass_wide128_f32);
+            # GD_SPMM_D128_FORM=items keeps the one-row items of the vector kernel (A/B)
+            items, n_items, bounds, tags = plan.onepass_wide128()
+            check(_lib.lib().gd_spmm_csr_onepass_wide128_f32(ptr(items), n_items, ptr(_wide_col(plan, col, tags)), ptr(val), ptr(x), x.stride(0),
+                                                             ptr(y), y.stride(0), ptr(bias), float(self_coef), ptr(x_self), d, int(col.shape[0]),
+                                                             x_rows, ptr(bounds), stream_ptr(x.device)), 'gd_spmm_csr_onepass_wide128_f32')
+            return y
         items, n_items, bounds = plan.onepass(d)
         check(_lib.lib().gd_spmm_csr_onepass_f32(ptr(items), n_items, ptr(col), ptr(val), ptr(x), x.stride(0), ptr(y),
                                                  y.stride(0), ptr(bias), float(self_coef), ptr(x_self), d, int(col.shape[0]),

@@ -50,6 +50,7 @@ extern "C" {
                                 gd_edge_bce_f32, gd_col_sum_f32 (+ their _workspace queries): the fused backbone step (entries added: the version stays);
                                 gd_row_nll_f32 (+ its _workspace query): the fused node-classification step (entries added: the version stays);
                                 gd_spmm_csr_onepass_wide_f32: 64-float rows summed 16 rows per item on the matrix pipe (entry added: the version stays);
+                                gd_spmm_csr_onepass_wide128_f32: the same at 128-float rows (entry added: the version stays);
                                 gd_negative_edges: negative edges drawn on the device (entry added: the version stays);
                                 gd_edge_incidence_fixed, gd_edge_incidence_update (+ their size queries): the incidence list when only
                                 the tail of the decoded edges changes (entries added: the version stays);
@@ -205,6 +206,18 @@ int gd_spmm_csr_onepass_wide_f32(const int32_t* items, int32_t n_items, const in
                                  const float* x, int64_t ldx, float* y, int64_t ldy, const float* bias, float self_coef,
                                  const float* x_self, int32_t d, int32_t nnz, int32_t x_rows, const int32_t* xcd_bounds,
                                  void* stream);
+
+/* The wide form for rows of exactly 128 floats (entry added: the version stays).  Arguments, checks, items, col_tagged and
+ * xcd_bounds as for gd_spmm_csr_onepass_wide_f32 - the items and the row tags do not depend on the width - but d must be 128
+ * (any other width: GD_E_DIM).  A trip of four edges loads two float4 per lane from one source row and issues eight matrix
+ * instructions that share the one A value.  A GROUP member runs the vector path of gd_spmm_csr_onepass_f32 at d = 128 (two lane
+ * groups of 32 lanes): same trips, same summation order, the same bits as that entry.  Every other row is the fmaf chain over its
+ * own edges in item order, starting from the bias, + self_coef * x_self[row] at the end.  NON-FINITE INPUTS as above: a source row
+ * that holds Inf or NaN poisons every row of the items that gather it (0 x Inf = NaN inside the instruction). */
+int gd_spmm_csr_onepass_wide128_f32(const int32_t* items, int32_t n_items, const int32_t* col_tagged, const float* val,
+                                    const float* x, int64_t ldx, float* y, int64_t ldy, const float* bias, float self_coef,
+                                    const float* x_self, int32_t d, int32_t nnz, int32_t x_rows, const int32_t* xcd_bounds,
+                                    void* stream);
 
 /* gd_spmm_csr_onepass_f32 with the edge values read THROUGH a permutation from an interleaved (weight, addend) array kept in
  * another edge order (ABI 8): w[k] = aux[2 perm[k]], and aux_sum[row] = the sum of aux[2 perm[k] + 1] over the row's entries
