@@ -85,6 +85,12 @@ PROTOTYPES = {
                                            _p, _i64, _p]),
     'gd_batch_csr_workspace': (_i64, [_i32, _i64]),
     'gd_batch_csr': (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    'gd_induced_subgraph_typed_workspace': (_i64, [_i32]),
+    'gd_induced_subgraph_typed': (ctypes.c_int, [_p, _p, _p, _p, _i32, _i32, _p, _i32, _p, _i32, _p, _i64, _p, _p, _p, _p, _p, _p,
+                                                 _p, _p, _i64, _p]),
+    'gd_batch_typed_csr_workspace': (_i64, [_i32, _i64, _i32]),
+    'gd_batch_typed_csr': (ctypes.c_int, [_p, _p, _p, _i64, _i32, _i32, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                          _i64, _p]),
     'gd_batch_loss_terms_workspace': (_i64, [_i32, _i64]),
     'gd_batch_loss_terms': (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _f32, _f32, _p, _p, _p, _p, _p, _i64, _p]),
     'gd_rowpair_mse_workspace': (_i64, [_i32]),

@@ -145,6 +145,16 @@ class KGGNNDeleteNodeembTrainer(KGTrainer):
         _require_gpu()
         if getattr(args, 'fullgraph', False):
             return self.train_fullgraph(model, data, optimizer, args)
+        if getattr(args, 'fused_minibatch', False):
+            # --fused_minibatch (gnndelete_amd/minibatch.py): the batch cut, both typed convs, the losses, the backward and Adam
+            # on the HIP kernels
+            from ...minibatch import fused_minibatch_kg_unsupported, train_minibatch_kg_fused
+            reason = fused_minibatch_kg_unsupported(model, args, optimizer)
+            if reason is None:
+                self.trainer_log['minibatch_step'] = 'fused'
+                return train_minibatch_kg_fused(self, model, data, optimizer, args)
+            print(f'--fused_minibatch: {reason}; running the autograd mini-batch loop', flush=True)
+            self.trainer_log['minibatch_step'] = f'autograd: {reason}'
         loss_fct = get_loss_fct(self.args.loss_fct)
         model = model.to(device)
         data = data.to('cpu')

@@ -66,7 +66,7 @@ FLAGS = [
 EXTRA_FLAGS = [
     ('minibatch', None, False, 'train ogbl-* graphs on GraphSAINT mini-batches as upstream does (default: full graph)'),
     ('fullgraph', None, False, 'knowledge-graph unlearning (R-GCN): one fused full-graph step per epoch instead of the GraphSAINT batches upstream trains on'),
-    ('fused_minibatch', None, False, 'with --minibatch: run each GraphSAINT batch on the fused HIP batch step instead of the autograd loop (gnndelete_nodeemb and gnndelete trainers; GCN / GAT, MSE losses; train_gnn.py: the original model\'s BCE link-prediction batches, GCN / GAT, one plain Adam)'),
+    ('fused_minibatch', None, False, 'with --minibatch: run each GraphSAINT batch on the fused HIP batch step instead of the autograd loop (gnndelete_nodeemb and gnndelete trainers; GCN / GAT, MSE losses; train_gnn.py: the original model\'s BCE link-prediction batches, GCN / GAT, one plain Adam); delete_gnn.py --gnn rgcn on a knowledge graph (its default 64-root batches, no --minibatch needed): R-GCN, both_layerwise, two plain Adams)'),
     ('fused_edgeprob', None, False, 'with --unlearning_model gnndelete: run the full-graph edge-probability step on the fused HIP engine (GCN / GAT, one Adam) instead of the autograd loop'),
     ('fused_backbone', None, False, 'train_gnn.py and --unlearning_model retrain: run the full-batch link-prediction training step on the fused HIP engine (GCN / GAT, one plain Adam) instead of the autograd loop; train_node.py: the node-classification (NLL) training step likewise, up to 256 classes'),
     ('device_negatives', None, False, 'where --fused_backbone / --fused_edgeprob applies: draw each epoch\'s negatives on the device (seeded by --random_seed; a different random stream than the host sampler) and merge them into the decoder\'s incidence list there, no host work between epochs'),

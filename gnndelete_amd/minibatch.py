@@ -29,7 +29,13 @@ MinibatchBackboneStep is the batch step of the ORIGINAL model's training (train_
 framework/trainer/base.py:144-227): every parameter trains, so there is no frozen layer-1 table - each batch computes
 x[nodes] W1^T with the current W1 (gd_rows_gather_gemm_f32), runs both layers over the CSR of all batch edges, the BCE
 link-prediction loss over [batch edges | negatives] (gd_edge_bce_f32) and BackboneEngine's backward, then Adam on every
-parameter."""
+parameter.
+
+MinibatchKGNodeembStep is the batch step of the knowledge-graph trainer (delete_gnn.py --gnn rgcn --fused_minibatch;
+framework/trainer/gnndelete_nodeemb.py:659-846): a typed cut (gd_induced_subgraph_typed: the batch's Dr edges with their
+relation types, the decoded Df triples, the two row lists), the batch's node-major typed graphs (gd_batch_typed_csr: the
+arrays of graph.TypedNodeCSR), both R-GCN convs on gd_rgcn_conv_f32, negatives from utils.negative_sampling_kg, the loss
+stage and the layer-wise update of MinibatchNodeembStep."""
 import os
 
 import numpy as np
@@ -862,3 +868,357 @@ def train_minibatch_backbone_fused(trainer, model, data, optimizer, args, step_h
     torch.save({'model_state': model.state_dict(), 'optimizer_state': optimizer.state_dict()},
                os.path.join(args.checkpoint_dir, 'model_final.pt'))
     trainer.trainer_log['best_epoch'], trainer.trainer_log['best_valid_loss'] = best_epoch, best_valid_loss
+
+
+# ------------------------------------------------------------------------------------------------ knowledge-graph batches
+N_COUNTS_KG = 6        # gd_induced_subgraph_typed's count vector
+
+
+def fused_minibatch_kg_unsupported(model, args, optimizer):
+    """None when the fused knowledge-graph batch step applies (KGGNNDeleteNodeembTrainer.train with --fused_minibatch), else the
+    reason it does not (one line)."""
+    from .framework.trainer.sampler import data_parallel_world
+    from .nn import RGCNConv
+    conv1, conv2 = getattr(model, 'conv1', None), getattr(model, 'conv2', None)
+    if (not (type(conv1) is RGCNConv and type(conv2) is RGCNConv) or not hasattr(model, 'deletion1')
+            or not hasattr(model, 'node_emb')):
+        return f'no fused knowledge-graph batch step for the {type(model).__name__} backbone (R-GCN only)'
+    if getattr(args, 'loss_fct', 'mse_mean') not in ('mse_mean', 'mse_sum'):
+        return f'--loss_fct {args.loss_fct} is not an MSE loss'
+    if getattr(args, 'loss_type', 'both_layerwise') != 'both_layerwise':
+        return f'--loss_type {args.loss_type} (the fused step is the layer-wise update)'
+    for conv in (conv1, conv2):
+        nb = 1 if conv.num_blocks is None else int(conv.num_blocks)
+        d_in, d_out = int(conv.in_channels), int(conv.out_channels)
+        if not (0 < d_in <= 128 and 0 < d_out <= 128 and d_in % nb == 0 and d_out % nb == 0 and (d_in // nb) % 2 == 0
+                and (d_out // nb) % 2 == 0):
+            return f'widths {d_in} -> {d_out} in {nb} blocks (gd_rgcn_conv_f32 takes even block widths up to 128 floats)'
+    if not isinstance(optimizer, (list, tuple)) or len(optimizer) != 2:
+        return 'the optimizer is not two plain torch.optim.Adam'
+    for opt, p in zip(optimizer, (model.deletion1.deletion_weight, model.deletion2.deletion_weight)):
+        g = opt.param_groups[0]
+        if (type(opt) is not torch.optim.Adam or len(opt.param_groups) != 1 or g.get('weight_decay', 0) or g.get('amsgrad')
+                or g.get('maximize') or [id(q) for q in g['params']] != [id(p)]):
+            return 'the optimizer is not two plain torch.optim.Adam'
+    if data_parallel_world()[1] > 1:
+        return 'torch.distributed with more than one rank'
+    return None
+
+
+class _TypedBatchGraph:
+    __slots__ = ('n', 'n_edges', 'fwd', 'bwd', 'status')
+
+
+class KGBatchCut:
+    """The device side of a knowledge-graph GraphSAINT batch: the sampler's source-major CSR with one relation type and one
+    flag byte per edge (packed once per run), the node-sized relabel array, and buffers for gd_induced_subgraph_typed's
+    outputs (node buffers sized to the batch upper bound, edge buffers grown geometrically when a cut reports more)."""
+
+    def __init__(self, data, loader, dev, num_edge_type, max_nodes=None):
+        self.dev = dev
+        self.n = int(loader.n)
+        self.num_edge_type = int(num_edge_type)
+        self.rowptr32 = loader.rowptr.to(device=dev, dtype=torch.int32).contiguous()
+        self.col32 = loader.dst_sorted.to(device=dev, dtype=torch.int32).contiguous()
+        order = loader.order.to(data.edge_type.device)
+        self.edge_type32 = data.edge_type[order].to(device=dev, dtype=torch.int32).contiguous()
+        flags = data.dr_mask.to(torch.uint8) | (data.df_mask.to(torch.uint8) << 1)
+        self.edge_flags = flags[order.to(flags.device)].to(dev).contiguous()
+        node_flags = (data.sdf_node_1hop_mask_non_df_mask.to('cpu', torch.uint8)
+                      | (data.sdf_node_2hop_mask_non_df_mask.to('cpu', torch.uint8) << 1))
+        self.node_flags = node_flags.to(dev).contiguous()
+        self.relabel = torch.zeros(self.n, dtype=torch.int64, device=dev)
+        self.generation = 0
+        self.counts = torch.zeros(N_COUNTS_KG, dtype=torch.int32, device=dev)
+        self.n_cap = self.e_cap = 0
+        self._bufs = {}
+        self._ensure(max_nodes or 1024, 4 * (max_nodes or 1024))
+        self.reads = 0                  # blocking host reads made by the cut (the count vector)
+
+    _ws = BatchCut._ws
+
+    def _ensure(self, n_b, e):
+        if n_b <= self.n_cap and e <= self.e_cap:
+            return
+        self.n_cap, self.e_cap = max(self.n_cap, _grow(n_b)), max(self.e_cap, _grow(e))
+        dev, n, c = self.dev, self.n_cap, self.e_cap
+        self.dr = torch.empty(3, c, dtype=torch.int32, device=dev)              # src, dst, type
+        self.df_index = torch.empty(2, c, dtype=torch.int64, device=dev)
+        self.df_type = torch.empty(c, dtype=torch.int64, device=dev)
+        self.row_lists = torch.empty(2 * n, dtype=torch.int32, device=dev)      # list k at k * n_b
+        self.seg_row = torch.arange(n, dtype=torch.int32, device=dev)
+
+    def cut(self, nodes):
+        """gd_induced_subgraph_typed on one sorted, unique node set -> the host copy of the count vector."""
+        nodes = nodes.to(self.dev, torch.int64).contiguous()
+        n_b = int(nodes.numel())
+        self._ensure(n_b, 0)
+        self.generation += 1
+        L = _lib.lib()
+        while True:
+            ws = self._ws('cut', L.gd_induced_subgraph_typed_workspace(n_b))
+            check(L.gd_induced_subgraph_typed(ptr(self.rowptr32), ptr(self.col32), ptr(self.edge_type32), ptr(self.edge_flags),
+                                              self.n, self.num_edge_type, ptr(nodes), n_b, ptr(self.node_flags), self.generation,
+                                              ptr(self.relabel), self.e_cap, ptr(self.dr[0]), ptr(self.dr[1]), ptr(self.dr[2]),
+                                              ptr(self.df_index), ptr(self.df_type), ptr(self.row_lists), ptr(self.counts), ptr(ws),
+                                              ws.numel(), stream_ptr(self.dev)), 'gd_induced_subgraph_typed')
+            cnt = self.counts.tolist()
+            self.reads += 1
+            if max(cnt[1], cnt[2]) <= self.e_cap:
+                break
+            self._ensure(n_b, max(cnt[1], cnt[2]))         # the edge outputs were not written: grow, cut again
+        if cnt[5]:
+            raise IndexError(f'batch node ids outside [0, {self.n})')
+        self.nodes, self.cnt = nodes, cnt
+        return cnt
+
+    def rows(self, k, count):
+        """Batch rows of the latest cut with node flag bit k (0: list 1, 1: list 2), ascending: int32 [count]."""
+        n_b = self.cnt[0]
+        return self.row_lists[k * n_b:k * n_b + count]
+
+    def typed_graph(self, n_rel):
+        """gd_batch_typed_csr over the latest cut's Dr edges: the arrays of graph.TypedNodeCSR(...).fwd / .bwd."""
+        return batch_typed_csr(self.dr[0], self.dr[1], self.dr[2], self.cnt[1], self.cnt[0], n_rel, self._bufs)
+
+
+def batch_typed_csr(src, dst, etype, n_edges, n_nodes, n_rel, bufs=None, into=None):
+    """gd_batch_typed_csr on n_edges typed edges (int32 device arrays) -> a _TypedBatchGraph whose fwd / bwd are
+    (node_ptr, seg_ptr, seg_rel, col, w) with room for n_edges runs; status [4] stays on the device.  into: a graph of the
+    same sizes whose arrays are written again."""
+    dev = src.device
+    L = _lib.lib()
+    e = int(n_edges)
+    g = into
+    if g is None or (g.n, g.n_edges) != (int(n_nodes), e):
+        g = _TypedBatchGraph()
+        g.n, g.n_edges = int(n_nodes), e
+        i32 = dict(dtype=torch.int32, device=dev)
+        sides = []
+        for _ in range(2):
+            sides.append((torch.empty(g.n + 1, **i32), torch.empty(e + 1, **i32), torch.empty(max(e, 1), **i32),
+                          torch.empty(max(e, 1), **i32), torch.empty(max(e, 1), dtype=torch.float32, device=dev)))
+        g.fwd, g.bwd = sides
+        g.status = torch.empty(4, **i32)
+    nbytes = L.gd_batch_typed_csr_workspace(g.n, e, int(n_rel))
+    if nbytes < 0:
+        raise ValueError('batch_typed_csr: batch too large for int32 indices')
+    if bufs is None:
+        ws = torch.empty(max(256, nbytes), dtype=torch.uint8, device=dev)
+    else:
+        ws = bufs.get('typed_csr')
+        if ws is None or ws.numel() < nbytes:
+            ws = bufs['typed_csr'] = torch.empty(max(256, _grow(nbytes)), dtype=torch.uint8, device=dev)
+    check(L.gd_batch_typed_csr(ptr(src), ptr(dst), ptr(etype), e, g.n, int(n_rel), max(e, 1), e, *(ptr(t) for t in g.fwd),
+                               *(ptr(t) for t in g.bwd), ptr(g.status), ptr(ws), ws.numel(), stream_ptr(dev)),
+          'gd_batch_typed_csr')
+    return g
+
+
+class MinibatchKGNodeembStep(_BatchLayers):
+    """One batch of KGGNNDeleteNodeembTrainer.train (gnndelete_nodeemb.py:659-846 of the reference) with an explicit forward, a
+    hand-derived backward and the library's Adam: the typed cut, the batch's two typed graphs, both R-GCN convs on
+    gd_rgcn_conv_f32 (root and bias through the row GEMM), the Del rows, negatives from utils.negative_sampling_kg, DEC + NI of
+    both layers on gd_batch_loss_terms + gd_rowpair_mse_f32, then loss 1 -> Adam on W_D1, loss 2 -> Adam on W_D2 while its
+    W_D1 gradient (through conv2 transposed, the ReLU gate and the Del-1 rows) waits for the next batch.  Shapes change per
+    batch: eager launches, no captured graph, one blocking host read (the count vector)."""
+
+    def __init__(self, model, data, loader, num_edge_type, alpha, reduction, lr, betas, eps, max_nodes=None):
+        dev = next(model.parameters()).device
+        self.dev, self.model, self.gat = dev, model, False
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.alpha, self.reduction = float(alpha), reduction
+        self.cut = KGBatchCut(data, loader, dev, num_edge_type, max_nodes)
+        c1, c2 = self.convs = (model.conv1, model.conv2)
+        self.n_rel = int(c1.num_relations)
+        self.nb = tuple(1 if c.num_blocks is None else int(c.num_blocks) for c in self.convs)
+        self.emb = model.node_emb.weight.detach().to(torch.float32).contiguous()
+        self.emb_ids = data.x.to(dev, torch.int64).reshape(-1).contiguous()
+        self.weights = tuple(c.weight.detach().contiguous() for c in self.convs)
+        self.roots = tuple(c.root.detach().contiguous() for c in self.convs)              # [in, out]
+        self.biases = tuple(c.bias.detach().contiguous() for c in self.convs)
+        self.H, self.O = int(c1.out_channels), int(c2.out_channels)
+        self.wd1, self.wd2 = model.deletion1.deletion_weight, model.deletion2.deletion_weight
+        self.adam = []
+        for p in (self.wd1, self.wd2):
+            self.adam.append({'m': torch.zeros_like(p.data), 'v': torch.zeros_like(p.data),
+                              'step': torch.zeros(1, dtype=torch.int32, device=dev), 'steps': 0})
+        self.g1 = torch.zeros_like(self.wd1.data)
+        self.g2 = torch.zeros_like(self.wd2.data)
+        self.g1_live = False            # W_D1 holds loss2's gradient of the previous batch (carried into the next step)
+        self._bufs = {}
+        self.events = None              # list -> (stage, cuda event) pairs are appended (stage split of the experiment)
+
+    _adam = _BatchStep._adam
+    import_adam_state = MinibatchNodeembStep.import_adam_state
+    export_adam_state = MinibatchNodeembStep.export_adam_state
+
+    # ---------------------------------------------------------------------------------------------- layers
+    def _typed(self, arrays, x, k, trans, y):
+        """y += the typed aggregation of conv k over one side of the batch graph (gd_rgcn_conv_f32, no plan)."""
+        node_ptr, seg_ptr, seg_rel, col, w = arrays
+        check(_lib.lib().gd_rgcn_conv_f32(ptr(node_ptr), ptr(seg_ptr), ptr(seg_rel), ptr(col), ptr(w), ptr(x), x.stride(0),
+                                          x.shape[1], ptr(self.weights[k]), self.nb[k], int(trans), ptr(y), y.stride(0),
+                                          y.shape[1], y.shape[0], stream_ptr(self.dev)), 'gd_rgcn_conv_f32')
+        return y
+
+    def _conv(self, k, g, x):
+        """conv k of the frozen backbone on the batch graph: x root + bias + the per-relation means times W_r."""
+        y = ops.rows_gemm(x, None, self.roots[k], trans_w=False, bias=self.biases[k])
+        if g.n_edges:
+            self._typed(g.fwd, x, k, 0, y)
+        return y
+
+    def _loss(self, z, z_ori, neg, n_pos, ni, n_ni, d, sums):
+        """DEC + NI of one layer: sums[0] += sum of squared DEC differences, sums[1] += NI's; -> dz of alpha * DEC + (1 - alpha)
+        * NI under the run's reduction (a mean over zero rows has no gradient)."""
+        L = _lib.lib()
+        c = self.cut
+        n_b = c.cnt[0]
+        n_terms = 2 * n_pos + n_ni
+        if self.reduction == 'mean':
+            w_dec = self.alpha / (2 * n_pos * d) if n_pos else 0.0
+            w_ni = (1.0 - self.alpha) / (n_ni * d) if n_ni else 0.0
+        else:
+            w_dec, w_ni = self.alpha, 1.0 - self.alpha
+        seg_ptr = torch.empty(n_b + 1, dtype=torch.int32, device=self.dev)
+        term_o = torch.empty(max(n_terms, 1), dtype=torch.int32, device=self.dev)
+        term_w = torch.empty(max(n_terms, 1), dtype=torch.float32, device=self.dev)
+        term_kind = torch.empty(max(n_terms, 1), dtype=torch.int32, device=self.dev)
+        ws = self._ws('terms', L.gd_batch_loss_terms_workspace(n_b, n_terms))
+        check(L.gd_batch_loss_terms(ptr(c.df_index), c.e_cap, ptr(neg), neg.stride(0) if n_pos else 0, n_pos, ptr(ni), n_ni, n_b,
+                                    w_dec, w_ni, ptr(seg_ptr), ptr(term_o), ptr(term_w), ptr(term_kind), ptr(ws), ws.numel(),
+                                    stream_ptr(self.dev)), 'gd_batch_loss_terms')
+        dz = torch.empty(n_b, d, dtype=torch.float32, device=self.dev)
+        part = torch.empty(max(1, L.gd_rowpair_mse_workspace(n_b)), dtype=torch.float32, device=self.dev)
+        check(L.gd_rowpair_mse_f32(ptr(z), z.stride(0), ptr(z_ori), z_ori.stride(0), d, ptr(seg_ptr), ptr(c.seg_row), n_b,
+                                   ptr(term_o), ptr(term_w), ptr(term_kind), ptr(dz), dz.stride(0), 0, ptr(sums), ptr(part),
+                                   stream_ptr(self.dev)), 'gd_rowpair_mse_f32')
+        return dz
+
+    # ---------------------------------------------------------------------------------------------- one batch
+    @torch.no_grad()
+    def step(self, nodes, sums):
+        """One batch of the layer-wise update on `nodes`; sums [4] (zeroed by the caller) receives the squared-difference
+        sums (DEC 1, NI 1, DEC 2, NI 2).  Returns the divisors that turn them into the loop's four loss terms."""
+        from .framework import utils as U
+        self._mark('start')
+        c = self.cut
+        cnt = c.cut(nodes)
+        n_b, m_df, n_l1, n_l2 = cnt[0], cnt[2], cnt[3], cnt[4]
+        self._mark('cut')
+        g = c.typed_graph(self.n_rel)
+        self._mark('csr')
+        H, O = self.H, self.O
+        idx1, idx2 = c.rows(0, n_l1), c.rows(1, n_l2)
+        wd1, wd2 = self.wd1.data, self.wd2.data
+        # forward: the frozen convs on the batch's Dr graph; conv1's output is z1_ori AND the Del-1 input
+        x = self.emb.index_select(0, self.emb_ids.index_select(0, c.nodes))
+        z1_ori = self._conv(0, g, x)
+        z2_ori = self._conv(1, g, torch.relu(z1_ori))
+        z1 = z1_ori.clone()
+        if n_l1:
+            ops.rows_gemm(z1_ori, idx1, wd1, out=z1)
+        a1 = torch.relu(z1)
+        p2 = self._conv(1, g, a1)
+        z2 = p2.clone()
+        if n_l2:
+            ops.rows_gemm(p2, idx2, wd2, out=z2)
+        self._mark('forward')
+        dec_index, dec_type = c.df_index[:, :m_df], c.df_type[:m_df]
+        neg = U.negative_sampling_kg(edge_index=dec_index, edge_type=dec_type).to(self.dev, torch.int64).contiguous()
+        self._mark('negatives')
+        dz1 = self._loss(z1, z1_ori, neg, m_df, idx1, n_l1, H, sums[0:2])
+        dz2 = self._loss(z2, z2_ori, neg, m_df, idx2, n_l2, O, sums[2:4])
+        self._mark('loss')
+        # loss1: W_D1's gradient (+ what loss2 left on it last batch), Adam.  The Del layer's autograd node always returns a
+        # weight gradient (zeros without rows), so neither parameter is ever skipped by the loop's Adams and none is here.
+        if n_l1:
+            ops.rows_gemm_wgrad(z1_ori, idx1, dz1, idx1, n_l1, out=self.g1, accumulate=self.g1_live)
+        elif not self.g1_live:
+            self.g1.zero_()
+        self._adam(0, self.wd1, self.g1)
+        # loss2: W_D2's gradient and, through conv2 (root + the transposed typed graph), the ReLU gate and the Del-1 rows, a
+        # fresh W_D1 gradient that waits for the next batch
+        if n_l2:
+            ops.rows_gemm_wgrad(p2, idx2, dz2, idx2, n_l2, out=self.g2)
+        else:
+            self.g2.zero_()
+        if n_l1:
+            dp2 = dz2.clone()
+            if n_l2:
+                ops.rows_gemm(dz2, idx2, wd2, trans_w=True, out=dp2)
+            dx1 = ops.rows_gemm(dp2, None, self.roots[1], trans_w=True)              # [n_b, H], before the ReLU gate
+            if g.n_edges:
+                self._typed(g.bwd, dp2, 1, 1, dx1)
+            ops.rows_gemm_wgrad(z1_ori, idx1, dx1, idx1, n_l1, relu_mask=z1, out=self.g1)
+        else:
+            self.g1.zero_()
+        self.g1_live = True
+        self._adam(1, self.wd2, self.g2)
+        self._mark('backward')
+        if self.reduction == 'mean':
+            return (2 * m_df * H, n_l1 * H, 2 * m_df * O, n_l2 * O)
+        return (1, 1, 1, 1)
+
+
+def _kg_step_log(epoch, sums, div, alpha):
+    """The knowledge-graph loop's step record from the four squared-difference sums (fp32, as MSELoss computes them)."""
+    f = np.float32
+    with np.errstate(divide='ignore', invalid='ignore'):
+        r1, l1, r2, l2 = (f(s) / f(d) for s, d in zip(sums, div))
+        loss1 = f(alpha) * r1 + f(1 - alpha) * l1
+        loss2 = f(alpha) * r2 + f(1 - alpha) * l2
+        return {'Epoch': epoch, 'train_loss': float(loss1 + loss2), 'loss_r': float(r1 + r2), 'loss_l': float(l1 + l2)}
+
+
+def train_minibatch_kg_fused(trainer, model, data, optimizer, args, step_hook=None):
+    """KGGNNDeleteNodeembTrainer.train's batch loop with the batch step on the HIP kernels: same sampler and negatives (same
+    host random stream), same update order, step records (read once per epoch), validation cadence, model selection and
+    checkpoints."""
+    from .framework.trainer import sampler as S
+    from .framework.trainer._log import wandb_log
+    from .framework.trainer.base import _require_gpu, device
+    from .framework.trainer.gnndelete_nodeemb import _adam_hyper, _non_df_masks
+    _require_gpu()
+    model = model.to(device)
+    data = data.to('cpu')
+    _non_df_masks(data)
+    loader = S.make_sampler(data, args.batch_size, args.num_steps)
+    lr, betas, eps = _adam_hyper(optimizer)
+    alpha = trainer.args.alpha
+    step = MinibatchKGNodeembStep(model, data, loader, trainer.args.num_edge_type, alpha,
+                                  'mean' if trainer.args.loss_fct == 'mse_mean' else 'sum', lr, betas, eps,
+                                  max_nodes=(loader.walk_length + 1) * max(int(loader.batch_size), 1))
+    step.import_adam_state(optimizer)
+    trainer._fused_minibatch_step = step
+    best_metric = 0
+    trainer.trainer_log['steps'] = []
+    for epoch in range(args.epochs):
+        model.train()
+        hist = torch.zeros(max(len(loader), 1), 4, dtype=torch.float32, device=device)
+        divs = []
+        for i, nodes in enumerate(loader.node_sets()):
+            if i >= hist.shape[0]:
+                hist = torch.cat([hist, torch.zeros_like(hist)])
+            divs.append(step.step(nodes, hist[i]))
+            if step_hook is not None:
+                step_hook(step)
+        last = None
+        for s4, div in zip(hist[:len(divs)].tolist(), divs):                 # the epoch's host read
+            last = _kg_step_log(epoch, s4, div, alpha)
+            wandb_log(last)
+            trainer.trainer_log['steps'].append(last)
+        if (epoch + 1) % trainer.args.valid_freq == 0 and last is not None:
+            valid_loss, dt_auc, dt_aup, df_auc, df_aup, df_logit, _, valid_log = trainer.eval(model, data, 'val')
+            valid_log['epoch'] = epoch
+            trainer._record({'epoch': epoch, 'train_loss': last['train_loss'], 'loss_r': last['loss_r'],
+                             'loss_l': last['loss_l']}, valid_log)
+            if dt_auc + df_auc > best_metric:
+                best_metric = dt_auc + df_auc
+                print(f'Save best checkpoint at epoch {epoch:04d}. Valid loss = {valid_loss:.4f}')
+                torch.save({'model_state': model.state_dict()}, os.path.join(args.checkpoint_dir, 'model_best.pt'))
+            data = data.to('cpu')
+    step.export_adam_state(optimizer)
+    torch.save({'model_state': {k: v.to('cpu') for k, v in model.state_dict().items()}},
+               os.path.join(args.checkpoint_dir, 'model_final.pt'))

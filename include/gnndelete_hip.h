@@ -65,7 +65,9 @@ extern "C" {
                                 gd_subset_rank_metrics_drawn, gd_subset_draw: the 500 validation subsets drawn inside the rank kernel
                                 (entries added: the version stays);
                                 gd_rows_gemm_select_chain_f32 (+ its _covers query): conv1's explicit rows formed inside conv2's Linear
-                                (entries added: the version stays) */
+                                (entries added: the version stays);
+                                gd_induced_subgraph_typed, gd_batch_typed_csr (+ their _workspace queries): the knowledge-graph
+                                GraphSAINT batch step (entries added: the version stays) */
 
 enum {
   GD_OK = 0,
@@ -1234,6 +1236,43 @@ int gd_batch_loss_terms(const int64_t* pos, int64_t ld_pos, const int64_t* neg, 
                         const int32_t* ni, int32_t n_ni, int32_t n_b, float w_dec, float w_ni, int32_t* seg_ptr,
                         int32_t* term_o, float* term_w, int32_t* term_kind, void* workspace, int64_t workspace_bytes,
                         void* stream);
+
+/* gd_induced_subgraph for a KNOWLEDGE graph (KGGNNDeleteNodeembTrainer.train, framework/trainer/gnndelete_nodeemb.py:659-846 of
+ * the reference; RandomWalkSubgraphSampler.subgraph followed by the trainer's dr_mask / df_mask / forward-type masking here), same
+ * conventions: rowptr / col as above, edge_type [E] int32 and edge_flags [E] in that order (bit 0 = dr_mask, bit 1 = df_mask -
+ * parallel edges of one pair keep their input order, so do their types), node_flags bit 0 = list 1
+ * (sdf_node_1hop_mask_non_df_mask), bit 1 = list 2 (the 2-hop one): the Del rows AND the NI rows of the two layers.
+ * Outputs (device), all in batch ids:
+ *   dr_src / dr_dst / dr_type [edge_cap] int32: the batch's Dr edges, in subgraph() order (message passing)
+ *   df_index [2, edge_cap] int64 (row 1 at + edge_cap), df_type [edge_cap] int64: the Df triples with type < num_edge_type, in
+ *           subgraph() order (the decoded positives; what negative_sampling_kg reads)
+ *   row_lists [2, n_b] int32: batch rows with node flag bit k, ascending, list k at row_lists + k * n_b
+ *   counts [6] int32: n_b, Dr edges, decoded Df triples, |list 1|, |list 2|, and 1 if a node id was outside [0, n_nodes)
+ *           (such rows are cut as empty).  When either edge count exceeds edge_cap, counts is written and no edge output is.
+ *   workspace >= gd_induced_subgraph_typed_workspace(n_b) bytes, 256-byte aligned.  Integer only, bit-exact; no memset. */
+int64_t gd_induced_subgraph_typed_workspace(int32_t n_b);
+int gd_induced_subgraph_typed(const int32_t* rowptr, const int32_t* col, const int32_t* edge_type, const uint8_t* edge_flags,
+                              int32_t n_nodes, int32_t num_edge_type, const int64_t* nodes, int32_t n_b, const uint8_t* node_flags,
+                              int32_t generation, int64_t* relabel, int64_t edge_cap, int32_t* dr_src, int32_t* dr_dst,
+                              int32_t* dr_type, int64_t* df_index, int64_t* df_type, int32_t* row_lists, int32_t* counts,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+
+/* graph.TypedNodeCSR(edge_index, edge_type, n_nodes, n_rel) for a batch, without a host round trip: the two node-major typed
+ * graphs gd_rgcn_conv_f32 reads, from n_edges typed edges (src, dst, type int32, any order).
+ *   node_ptr [n_nodes + 1], seg_ptr [seg_cap + 1], seg_rel [seg_cap], col / w [edge_cap]: `fwd` - in-edges sorted by (target,
+ *           relation, source), w = 1 / |run| (one correctly rounded division);  the _t arrays: `bwd`, the transpose sorted by
+ *           (source, relation, target), every edge carrying the weight of the forward run it belongs to
+ *   status [4] int32 (device): runs of fwd, runs of bwd, 1 if an edge had an endpoint or relation out of range (it is left
+ *           out), 1 if seg_cap was too small (n_edges always suffices; edge_cap >= n_edges is required)
+ * Edges take a slot of their node's bucket by integer atomics and are then ranked inside the bucket by (relation, other
+ * endpoint, input position): the result does not depend on the order the atomics arrive in.  No float atomics; the counters are
+ * zeroed by the first launch; every store is guarded by the capacities.  The rank costs O(degree^2) per node: batch sizes.
+ * workspace >= gd_batch_typed_csr_workspace(n_nodes, n_edges, n_rel) bytes, 256-byte aligned (-1: n_nodes * n_rel >= 2^31). */
+int64_t gd_batch_typed_csr_workspace(int32_t n_nodes, int64_t n_edges, int32_t n_rel);
+int gd_batch_typed_csr(const int32_t* src, const int32_t* dst, const int32_t* type, int64_t n_edges, int32_t n_nodes, int32_t n_rel,
+                       int64_t edge_cap, int64_t seg_cap, int32_t* node_ptr, int32_t* seg_ptr, int32_t* seg_rel, int32_t* col,
+                       float* w, int32_t* node_ptr_t, int32_t* seg_ptr_t, int32_t* seg_rel_t, int32_t* col_t, float* w_t,
+                       int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- collectives (RCCL) ---- */
 
