@@ -59,13 +59,9 @@ def _kg_graph():
 
 
 def _reference(sampler, nodes):
-    """subgraph() + the trainer's masking (framework/trainer/kg.py: the Dr edges and types, the decoded Df triples, the rows)."""
-    b = sampler.subgraph(nodes)
-    dr_index, dr_type = b.edge_index[:, b.dr_mask], b.edge_type[b.dr_mask]
-    pos_index, pos_type = b.edge_index[:, b.df_mask], b.edge_type[b.df_mask]
-    fwd = pos_type < R
-    rows = [m.nonzero().flatten().to(torch.int32) for m in (b.sdf_node_1hop_mask_non_df_mask, b.sdf_node_2hop_mask_non_df_mask)]
-    return dr_index, dr_type, pos_index[:, fwd], pos_type[fwd], rows, pos_index.shape[1]
+    """subgraph() + the trainer's masking (kg_batch_cases.cut_reference, shared with the tests past one scan chunk)."""
+    from kg_batch_cases import cut_reference
+    return cut_reference(sampler, nodes, R)
 
 
 def _raw_cut(cut, nodes, cap, generation):
